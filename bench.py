@@ -11,11 +11,19 @@ the resident measurement.
 
 Default workload = BASELINE.json configs[3], the largest single-GPU config and the one north_star's
 targets are quoted on: Middlebury-2014 full resolution 3000x2000, D = 256, censusGrad + CBCA(2) +
-SolveAll + SGM 4-path + WTA, 2 pairs per GPU.  Every map rank 0's timed loop produced is checked
-bit-exact against the committed oracle map of that pair (tests/golden/bench_maps_<workload>.npz),
-and the one-stream per-kernel pass must reproduce them.  Other configs:
---workload teddy (configs[1], 16 pairs, CPU baseline on whole pairs with map comparison),
-kitti (configs[2]), hd (configs[4] per-GPU shard).  Prints ONE JSON line on rank 0.
+SolveAll + SGM 4-path + WTA, 2 pairs per GPU.  Other configs: --workload teddy (configs[1], 16
+pairs), kitti (configs[2]), hd (configs[4] per-GPU shard).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (throughput, ms_per_step, the
+bad-pixel rates of the timed maps) -- nothing else.  --dump-outputs DIR also writes the maps of
+the last timed step (what a caller of the timed path receives) as DIR/disp.npy, float32; the
+synthetic inputs are seeded, so two builds run with the same arguments can be compared map for map.
+
+--full adds every other leg, each outside the timed region: every map rank 0's timed loop produced
+is checked bit-exact against the committed oracle map of that pair
+(tests/golden/bench_maps_<workload>.npz), the one-stream per-kernel pass (HIP events, roofline,
+and its maps must equal the timed loop's), the copy ceiling, the schedule A/B, the 1-thread CPU
+baseline (teddy: whole pairs with map comparison) and, with N > 1, e2e_batch.
 """
 from __future__ import annotations
 
@@ -130,6 +138,24 @@ def _host_cpu():
     return f"{model}, {os.cpu_count()} logical CPUs"
 
 
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: upper bound of what one run writes
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: each array of `arrays` ({name: ndarray}) as dirpath/<name>.npy in float32
+    (the int16 maps convert exactly).  An array whose float32 form would exceed its share of
+    DUMP_MAX_BYTES is written as a fixed sample instead: the elements at the sorted flat indices a
+    generator seeded with 0 draws without replacement, the same for every run of one shape."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) - 4096   # (the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size * 4 > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -137,10 +163,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="fullres", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="pairs per GPU (0 = workload default)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP-event timing")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle-map comparison (timing probes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: oracle-map parity, "
+                         "per-kernel HIP-event pass and roofline, copy ceiling, schedule A/B, CPU baseline, and "
+                         "(N > 1) e2e_batch; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps of the last timed step as DIR/disp.npy (float32; a fixed seeded sample of "
+                         "the pixels when the maps exceed 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU-baseline sample budget")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip per-kernel HIP-event timing")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle-map comparison (timing probes)")
     ap.add_argument("--no-d2h", action="store_true",
                     help="leave the maps in HBM at the end of a step (default: every timed step ends with the "
                          "int16 maps in pinned host memory, SURVEY §8d's `disp_out` ready)")
@@ -152,7 +185,8 @@ def parse():
                     help="CBCA: fuse iteration k's normalising sweep with iteration k+1's scan (sm_params.fuse_norm_scan; "
                          "auto = for volumes >= 256 MiB per pair)")
     ap.add_argument("--no-e2e-batch", action="store_true",
-                    help="N > 1: skip the DistributedBatchRunner steps reported as e2e_batch next to the resident line")
+                    help="--full, N > 1: skip the DistributedBatchRunner steps reported as e2e_batch next to the "
+                         "resident line")
     ap.add_argument("--e2e", action="store_true",
                     help="time the product multi-GPU path instead of resident batches: rank 0 holds the global "
                          "batch on the host; each step broadcasts the header, scatters the pairs (RCCL), runs "
@@ -266,15 +300,19 @@ def main():
         elapsed = float(t.item())
     # the maps the TIMED loop produced (its last step, default schedule): what parity is checked on
     disp = host_maps.copy() if host_maps is not None else sb.download()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"disp": disp})
     # the first run's volume placement trials (sm_params.placement_trials; in the warm-up)
     place_ms, place_kept = sb.placement()
+    # everything below that takes a run of its own belongs to --full
+    full = args.full
 
     # measured HBM ceiling next to the 8 TB/s spec: a dwordx4 copy over a buffer the
     # size of one pair's volume (at least 2 GiB, far past the 256 MB Infinity Cache).  After the
     # timed loop: run right before the warmup it slowed NL's first steps (Teddy x16 6.83 -> 7.32 ms
     # with three warmup steps, profiles/r5t)
     ceiling = None
-    if not args.no_profile:
+    if full and not args.no_profile:
         ceiling = sb.copy_ceiling(max(H * W * D * 4, 2 << 30), reps=5)
 
     # Schedule A/B on the SAME context (same device allocations, sm_set_schedule): the default
@@ -282,7 +320,7 @@ def main():
     # default can be checked against one stream without the per-instance placement spread
     # (DESIGN §6).  Reported beside the contract's timing, never instead of it.
     sched_ab = None
-    if not args.no_profile and args.streams != 1 and world == 1:
+    if full and not args.no_profile and args.streams != 1 and world == 1:
         sched_ab = {"default": [], "one_stream": []}
         for r in range(3):
             order = (("default", args.streams), ("one_stream", 1))
@@ -305,7 +343,7 @@ def main():
     # timed loop overlaps two groups of pairs, and a kernel's launch then shares the GPU with the
     # other group's kernels; the per-kernel pass runs the same pairs through a one-stream context
     # instead, so each duration (and the roofline below) is the kernel's own.
-    profile = not args.no_profile
+    profile = full and not args.no_profile
     kernels, ms_prof = {}, None
     kern_schedule = "one stream: the timed loop's own context" if args.streams == 1 else \
         "one stream (the timed loop's own context switched by sm_set_schedule): each kernel alone; the timed " \
@@ -328,7 +366,7 @@ def main():
         sbk.profile(False)
         sbk.set_schedule(args.streams, args.sub_batch)
     parity = fixture_check(args.workload, args.refine or args.agg != "CBCA", args.opt, disp, batch) \
-        if rank == 0 and not args.no_parity else None
+        if full and rank == 0 and not args.no_parity else None
     if profile and parity is not None:
         # the one-stream per-kernel pass must have produced the same maps
         if not np.array_equal(sb.download(), disp):
@@ -386,7 +424,7 @@ def main():
                                             "counted), grids 4K/16K/64K x 5 launches, best sample" % (max(H * W * D * 4, 2 << 30) / 1e9))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         host = _host_cpu()
         if H * W * D <= CPU_FULL_PAIR_MAX:
@@ -435,7 +473,7 @@ def main():
     # N > 1: the product batching path as well (configs[4]'s RCCL scatter / gather), timed after
     # the resident-batch line and reported beside it -- never instead of it
     e2e = None
-    if world > 1 and not args.no_e2e_batch:
+    if full and world > 1 and not args.no_e2e_batch:
         sb.close()
         e2e = _e2e_batch(args, world, rank, local, dist, backend, batch, H, W, md, paths, B)
 
@@ -443,7 +481,7 @@ def main():
         out = {
             "metric": METRIC, "value": round(value, 2), "unit": "Mdisp/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": bool(full),
             "data": "synthetic (seeded piecewise-planar pairs, mystereomatching_amd/synthetic.py)",
             "config": {"workload": desc, "H": H, "W": W, "D": D, "pairs_per_gpu": B, "global_batch": B * world,
                        "sgm_paths": paths, "aggregation": args.agg, "optimization": args.opt, "refine": bool(args.refine),
@@ -535,7 +573,8 @@ def _e2e_batch(args, world, rank, local, dist, backend, batch, H, W, md, paths, 
 def run_e2e(args, world, rank, local, dist, backend):
     """--e2e: DistributedBatchRunner.run timed end to end (host batch on rank 0 -> scatter ->
     compute -> gather -> host maps on rank 0).  value = pairs of the global batch x H x W x D per
-    second.  No roofline / CPU baseline here: the resident-batch line is the kernel measurement."""
+    second.  No roofline / CPU baseline here: the resident-batch line is the kernel measurement;
+    --full adds the oracle-map comparison of the last batch's maps."""
     import torch
     from mystereomatching_amd import synthetic as S
     from mystereomatching_amd.batch import DistributedBatchRunner, hip_compute_fn, sub_sizes
@@ -579,8 +618,10 @@ def run_e2e(args, world, rank, local, dist, backend):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"disp": maps})
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         parity = fixture_check(args.workload, False, "sgm", maps[:min(n, 64)])
     value = n * H * W * D * args.steps / elapsed / 1e6
     if rank == 0:

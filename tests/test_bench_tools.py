@@ -26,6 +26,32 @@ def test_kernel_symbol_groups():
     assert bench.kernel_symbol("cbca_v_norm_scan_r", 256, 4) == "cbca_v_norm_scan_r"   # its own instantiation
 
 
+def test_dump_outputs(tmp_path, monkeypatch):
+    import numpy as np
+    maps = np.arange(-7, 2 * 5 * 9 - 7, dtype=np.int16).reshape(2, 5, 9)
+    # small enough: written whole, float32, exact
+    bench.dump_outputs(str(tmp_path / "a"), {"disp": maps})
+    got = np.load(tmp_path / "a" / "disp.npy")
+    assert got.dtype == np.float32 and got.shape == maps.shape and np.array_equal(got, maps)
+    # over the byte budget: a fixed sample, the same from call to call, within the budget
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 4 * 40)
+    bench.dump_outputs(str(tmp_path / "b"), {"disp": maps})
+    bench.dump_outputs(str(tmp_path / "c"), {"disp": maps + 1})
+    b, c = np.load(tmp_path / "b" / "disp.npy"), np.load(tmp_path / "c" / "disp.npy")
+    assert b.dtype == np.float32 and b.shape == (40,) and np.array_equal(c, b + 1)
+    assert np.all(np.diff(b) > 0) and set(b.tolist()) <= set(maps.reshape(-1).tolist())
+    assert os.path.getsize(tmp_path / "b" / "disp.npy") <= bench.DUMP_MAX_BYTES
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
 def test_pmc_profile_names():
     seen = {}
     names = [pmc_summary.profile_name(s, seen) for s in (

@@ -1,4 +1,4 @@
-"""Print a bench.py JSON line as a short per-kernel table (tools/gpu_step.sh)."""
+"""Print a `bench.py --full` JSON line as a short per-kernel table."""
 import json
 import sys
 

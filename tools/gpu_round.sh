@@ -3,9 +3,9 @@
 # usage: tools/gpu_round.sh TAG STEP [STEP ...]     every step time-limited, chained with &&:
 #   tests            the whole -m gpu suite (-x)
 #   smoke            __graft_entry__.smoke()
-#   bench[:ARGS]     python bench.py ARGS (":"-separated args, e.g. bench:--workload:hd) -> bench_<n>.json
+#   bench[:ARGS]     python bench.py --full ARGS (":"-separated args, e.g. bench:--workload:hd) -> bench_<n>.json
 #   ab:WL:ROUNDS:COPIES:V1,V2,..   tools/ab_inproc.py on workload WL (variants as ab_inproc takes them)
-#   kt[:ARGS]        rocprofv3 --kernel-trace --stats of bench.py --streams 1 ARGS
+#   kt[:ARGS]        rocprofv3 --kernel-trace --stats of bench.py --full --streams 1 ARGS
 #   pmc[:ARGS]       FETCH_SIZE and WRITE_SIZE passes (separate runs) -> pmc_fullres_b2.json
 #   sq[:ARGS]        three SQ counter passes -> sq_fullres.json
 set -o pipefail
@@ -28,14 +28,14 @@ for step in "$@"; do
       tail -1 "$O/smoke.log" ;;
     bench)
       nb=$((nb + 1))
-      timeout -k 10 400 python bench.py $args > "$O/bench_$nb.json" 2> "$O/bench_$nb.err" || exit $?
+      timeout -k 10 400 python bench.py --full $args > "$O/bench_$nb.json" 2> "$O/bench_$nb.err" || exit $?
       cut -c1-400 "$O/bench_$nb.json" ;;
     ab)
       IFS=: read -r wl rounds copies vars <<< "$rest"
       timeout -k 10 900 python -u tools/ab_inproc.py --workload "$wl" --rounds "$rounds" --copies "$copies" ${vars//,/ } > "$O/ab_$wl.txt" 2>&1 || exit $?
       grep -v "^round" "$O/ab_$wl.txt" | tail -20 ;;
     kt)
-      (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o kt -- python3 "$R/bench.py" --streams 1 --steps 10 --warmup 2 --no-cpu-baseline $args > "$O/kt.log" 2>&1) || exit $?
+      (cd "$TMPDIR" && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o kt -- python3 "$R/bench.py" --full --streams 1 --steps 10 --warmup 2 --no-cpu-baseline $args > "$O/kt.log" 2>&1) || exit $?
       f=$(find "$O/kt" -name "*kernel_stats.csv" | head -1); cp "$f" "$O/kt_kernel_stats.csv"; head -12 "$O/kt_kernel_stats.csv" | cut -c1-200 ;;
     pmc)
       (cd /tmp && timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/pf" -o pmc -- python3 "$R/bench.py" --streams 1 --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-parity $args > "$O/pf.log" 2>&1 \

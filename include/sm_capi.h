@@ -151,6 +151,15 @@ typedef struct sm_params {
                                   * of memory during that call only; fewer if they do not fit).
                                   * -1 (default) = 3 with CBCA + SGM and a volume >= 256 MiB per
                                   * pair, else off; 0 / 1 = off; 2-8 = k */
+    int32_t fuse_cost_scan;      /* CBCA (results are identical for every setting): the first H scan
+                                  * of a view computes its censusGrad costs itself, so that view's
+                                  * cost volume is never written and read back (8 B per element
+                                  * less).  Applies to the views CBCA runs on, with censusGrad,
+                                  * >= 3 census words (more than 64 bits), lam_g == 1 and a grad_trunc
+                                  * at which the select-free cost elements apply; everything else
+                                  * keeps the cost-volume kernel.  1 = wherever eligible, 0 = never,
+                                  * -1 (default) = wherever eligible (measured faster at every
+                                  * bench shape, Teddy to full resolution) */
 } sm_params;
 
 typedef struct sm_ctx sm_ctx;

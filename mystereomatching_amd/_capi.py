@@ -43,6 +43,7 @@ class sm_params(C.Structure):
         ("gf_eps", C.c_float), ("gf_mode", C.c_int32), ("nl_sigma", C.c_double),
         ("lr_consis", C.c_int32),
         ("placement_trials", C.c_int32),
+        ("fuse_cost_scan", C.c_int32),
     ]
 
 

@@ -111,6 +111,7 @@ struct sm_ctx {
     float* luts = nullptr;      // device copy of lut_a | lut_b (per context: contexts on one device may differ)
     float ad_oor_exp = 0;
     bool fuse_norm_scan = false;
+    bool fuse_cost_scan = false;   // eligible views run the first H scan with the costs computed in it (cost_scan_fused)
     int num_cu = 256;           // compute units of the device
     int sub_batch = 0;          // sm_params.sub_batch: run sm_run in groups of k pairs (0 = all)
     int nstreams = 1;           // sm_params.num_streams: groups alternate over s streams (see sm_run)
@@ -125,7 +126,8 @@ struct sm_ctx {
     int dl_slot = 0;            // ev_dl slot of the next async download
     int dl_count = 0;
     hipEvent_t ev_up[2] = {};   // an async upload's copies done: main stream, side stream
-    hipEvent_t ev_in[2] = {};   // a pipelined run's group k has read its input images (after the cost volume)
+    hipEvent_t ev_in[2] = {};   // a pipelined run's group k has read its input images: recorded after the cost
+                                // volume, or (cost_scan_fused) after the last view's first CBCA sweep (in_ev)
     // (an early async upload goes on the null stream: the runtime spreads streams round-robin over
     // GPU_MAX_HW_QUEUES (4) in-order hardware queues, and a fifth stream of the context shared one
     // with a group or the map copies, whose kernels / copies the upload then waited behind; the
@@ -140,6 +142,8 @@ struct sm_ctx {
     std::vector<double> place_ms;   // the trials' pipeline times (sm_placement_trials_ms)
     int place_best = -1;
     std::vector<hipEvent_t> xev;                        // stagger / join events
+    hipEvent_t in_ev = nullptr;   // a pipelined group whose first CBCA sweep reads the input images: its "inputs
+                                  // read" event, recorded by run_cbca after the last view's first sweep
     hipEvent_t stagger_ev = nullptr;                    // SM_STAGGER_STAGE 1: recorded after the first CBCA sweep
     // profiling
     bool prof = false;
@@ -298,6 +302,7 @@ sm_status validate(const sm_params& p, std::string& why) {
     if (p.batch_capacity < 1) return bad("batch_capacity must be >= 1");
     if (p.sub_batch < 0 || p.num_streams < 0 || p.num_streams > 4) return bad("sub_batch >= 0 and num_streams in [0, 4] required");
     if (p.fuse_norm_scan < -1 || p.fuse_norm_scan > 1) return bad("fuse_norm_scan must be -1 (auto), 0 or 1");
+    if (p.fuse_cost_scan < -1 || p.fuse_cost_scan > 1) return bad("fuse_cost_scan must be -1 (auto), 0 or 1");
     if (p.placement_trials < -1 || p.placement_trials > 8) return bad("placement_trials must be in [-1, 8]");
     // The kernels rely on every cost and path cost being >= +0 (SGM and WTA minima compare float
     // bit patterns as unsigned integers, sm_device.h), which these constants guarantee: fusion
@@ -511,8 +516,21 @@ sm_status run_prep(sm_ctx* c, int n, const Bufs& B) {
     }
 }
 
+// The view's cost volume is not written: its first CBCA H scan computes the costs itself
+// (sm::launch_cbca_hsc, k_cost's select-free censusGrad elements with lamG == 1).  Only where CBCA
+// runs on the view -- a right view that is only built keeps its cost volume.
+bool cost_scan_fused(const sm_ctx* c, int view) {
+    const sm_params& p = c->p;
+    const int cw = (census_len(p) + 31) / 32;
+    return c->fuse_cost_scan && p.aggregation == SM_AGG_CBCA && p.cbca_iterations > 0 && view < n_views(p) &&
+           p.cost_method == SM_COST_CENSUS_GRAD && cw >= 3 && p.lam_g == 1.0f &&
+           sm::cost_nosel_ok(p.grad_trunc, p.lam_g, (float)census_len(p)) &&
+           sm::cbca_hsc_smem_bytes(cbca_lag(p), cw) <= 64 * 1024;
+}
+
 sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
     const sm_params& p = c->p;
+    if (cost_scan_fused(c, view)) return SM_OK;
     sm::CostArgs a{};
     a.vm = view == 0 ? B.vm0 : B.vm1;
     a.code = B.code;
@@ -567,8 +585,24 @@ sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const B
     // profile names: "cbca_h_scan" etc. for vm[0], "cbca_h_scan_r" etc. for vm[1]
     std::string sfx = view == 0 ? "" : "_r";
     auto nm = [&](const char* base) { static thread_local std::string t; t = std::string(base) + sfx; return t.c_str(); };
-    sm_status s = timed(c, nm("cbca_h_scan"), bytes, [&] { sm::launch_cbca(a, true, sm::CB_SCAN, n, c->st); });
+    sm_status s;
+    if (cost_scan_fused(c, view)) {   // the costs are computed in the sweep: it only writes the volume
+        a.code = B.code;
+        a.gray = B.gray;
+        a.lut = c->luts;
+        a.census_default = (float)census_len(p) * 1.0f;
+        a.grad_trunc = p.grad_trunc;
+        a.grad_adaptive = p.grad_adaptive;
+        a.cwords = (census_len(p) + 31) / 32;
+        s = timed(c, nm("cbca_h_scan_cost"), (double)n * c->nvol * 4.0, [&] { sm::launch_cbca_hsc(a, n, c->st); });
+    } else {
+        s = timed(c, nm("cbca_h_scan"), bytes, [&] { sm::launch_cbca(a, true, sm::CB_SCAN, n, c->st); });
+    }
     if (s) return s;
+    if (c->in_ev && view == n_views(p) - 1) {   // the last sweep that reads the group's input images
+        HIP_TRY(c, hipEventRecord(c->in_ev, c->st));
+        c->in_ev = nullptr;
+    }
     if (c->stagger_ev) {   // the next group may start: this group's next sweep is LDS- and issue-bound
         HIP_TRY(c, hipEventRecord(c->stagger_ev, c->st));
         c->stagger_ev = nullptr;
@@ -1028,6 +1062,7 @@ void sm_params_default(sm_params* p, int32_t max_disp, int32_t rows, int32_t col
     p->sub_batch = 0;
     p->num_streams = 0;        // auto (see sm_capi.h)
     p->fuse_norm_scan = -1;   // auto: fused where the lag-34 sweep applies or for volumes >= 256 MiB per pair
+    p->fuse_cost_scan = -1;   // auto (see sm_capi.h)
     p->gf_eps = 0.0001f;        // gf_eps[0] = 1e-4 (h:298; guidedFilter / guideFilterCore_matlab, cpp:4509-4513)
     p->gf_mode = SM_GF_XIMGPROC;  // `//#define MY_GUIDE` (h:38): the shipped build calls ximgproc::guidedFilter
     p->nl_sigma = 0.1;          // NLCCA::aggreCV (NL/NLCCA.cpp:33)
@@ -1184,6 +1219,11 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         // size (Teddy x16: 0.765 -> 0.692 ms, profiles/r4b/ab_teddy.txt)
         const bool nsv = cbca_lag(*p) == 34 && p->num_disparities % 64 == 0;
         c->fuse_norm_scan = p->fuse_norm_scan == 1 || (p->fuse_norm_scan == -1 && (nsv || c->nvol * 4 >= ((size_t)1 << 28)));
+        // auto = on: the fused sweep beat cost volume + H scan on all four bench workloads in
+        // same-process A/Bs (profiles/fuse_cost_scan/ab_*.txt: full resolution 6.30 -> 4.32 ms,
+        // 1080p 6.42 -> 5.06, KITTI 0.727 -> 0.548, Teddy x16 0.404 -> 0.334 ms), so there is no shape
+        // rule; cost_scan_fused decides per view whether the configuration is eligible
+        c->fuse_cost_scan = p->fuse_cost_scan != 0;
         if ((s = apply_schedule(c, p->num_streams, p->sub_batch))) return s;
         for (int i = 0; i < 16; i++) {
             hipEvent_t e;
@@ -1580,7 +1620,11 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
                 s_out = hip_fail(c, e, "hipEventCreate (inputs read)");
                 break;
             }
-            if ((e = hipEventRecord(c->ev_in[k], c->st)) != hipSuccess) {
+            // (a fused first CBCA sweep reads the gray images and census codes itself: run_cbca
+            // records the event after the last view's first sweep)
+            if (cost_scan_fused(c, 0)) {
+                c->in_ev = c->ev_in[k];
+            } else if ((e = hipEventRecord(c->ev_in[k], c->st)) != hipSuccess) {
                 s_out = hip_fail(c, e, "hipEventRecord (inputs read)");
                 break;
             }
@@ -1604,6 +1648,7 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
             break;
         }
         c->stagger_ev = nullptr;
+        c->in_ev = nullptr;
         if (ns > 1 && !early && (e = hipEventRecord(c->xev[1 + k % 8], c->st)) != hipSuccess) {
             s_out = hip_fail(c, e, "hipEventRecord (group CBCA done)");
             break;
@@ -1618,6 +1663,7 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     }
     c->st = main_st;
     c->stagger_ev = nullptr;
+    c->in_ev = nullptr;
     if (piped && !s_out) {
         c->pipe_live = true;   // group 1 stays on the side stream (joined by the next other call)
         c->pipe_g = g;
@@ -1790,7 +1836,8 @@ sm_status sm_upload_batch_async(sm_ctx* c, int32_t n, const uint8_t* lbgr, const
     const sm_params& p = c->p;
     const size_t H = p.rows, W = p.cols, crow = W * 3;
     // early: the copies go on their own stream as soon as each group's previous inputs are read
-    // (ev_in, recorded after its cost volume), so they overlap that group's CBCA and SGM; the
+    // (ev_in, recorded after its cost volume -- after its first CBCA sweep where that sweep computes
+    // the costs from the gray images itself, run_cbca), so they overlap that group's CBCA and SGM; the
     // group's next kernels wait for its copies (ev_up)
     const bool early = split && SM_UP_EARLY && c->ev_in[0] && c->ev_in[1];
     const hipStream_t ust = nullptr;

@@ -37,12 +37,15 @@
 // Rejected designs (same-process A/B) live as patches in tools/experiments/:
 // workgroup-staged V arm words, several waves / columns per block, persistent V sweeps, a per-tile
 // safe-dividend test, and the timing probes that located the V gathers' cost.
+// Superseded: cbca_h_scan_fused_cost.patch (the one-wave fusion of the censusGrad cost into the
+// first H scan, slower than the two kernels) by the multi-wave sweep k_cbca_hsc below.
 #include <float.h>
 #include <algorithm>
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sm_cost_elem.h"
 #include "sm_device.h"
 #include "sm_kernels.h"
 
@@ -1232,7 +1235,8 @@ __global__ __launch_bounds__(128) void k_cbca_nsv2(const CbcaArgs a) {
 // (both waves of HN2 run it: they write the same values)
 template <bool HORIZ, int MODE, bool FULL, bool SCALE, bool RV, int LAGC>
 __device__ __forceinline__ int cbca_line_setup(CbLine<HORIZ, MODE, FULL, SCALE, RV, LAGC>& L, const CbcaArgs& a,
-                                               const int blk, float* smem, const int prologue_sets = 0xff) {
+                                               const int blk, float* smem, const int prologue_sets = 0xff,
+                                               const int ztid = -1, const int zthreads = 64) {
     constexpr int T = CbCfg<HORIZ, MODE>::T;
     constexpr int NSETS = CbCfg<HORIZ, MODE>::NSETS;
     L.lane = (int)threadIdx.x & 63;
@@ -1310,7 +1314,8 @@ __device__ __forceinline__ int cbca_line_setup(CbLine<HORIZ, MODE, FULL, SCALE, 
     L.scale = a.scale;
     {   // zero the rings: reads of positions before the line start then yield S = 0, area = 0
         const int words = cbca_smem_words(a.lag, HORIZ, MODE);
-        for (int w = L.lane; w < words; w += 64) mine[w] = 0.f;
+        // (ztid >= 0: a workgroup of zthreads threads shares the zeroing)
+        for (int w = ztid < 0 ? L.lane : ztid; w < words; w += zthreads) mine[w] = 0.f;
     }
     __syncthreads();  // orders the float ring stores before the u16 ring reads
     L.S1 = L.S2 = 0.f;
@@ -1525,6 +1530,283 @@ template <bool FULL, bool SCALE, bool RV>
 __global__ __launch_bounds__(128) void k_cbca_hn2(const CbcaArgs a) {
     extern __shared__ float smem[];
     cbca_run_hn2<FULL, SCALE, RV>(a, xcd_swizzle(blockIdx.x, gridDim.x), smem);
+}
+
+// ---------------------------------------------------------------------------------------------
+// HSC: the first H scan of a view with its censusGrad costs computed in the workgroup, so that the
+// cost volume is never written and read back: the sweep only writes (4 B per element instead of
+// the cost kernel's 4 and the scan's 8).  One workgroup of 1 + NCW waves per (row, 64-disparity
+// chunk), lane = disparity:
+//  * the scan wave (wave 0) is CbLine<true, CB_SCAN>'s sweep as it stands (arm staging, S ring,
+//    stores); a tile's inputs t.x[k] come from an LDS hand-over buffer instead of the volume;
+//  * NCW cost waves evaluate k_cost's select-free element (cost_elem_nosel, sm_cost_elem.h: the
+//    same code) for T / NCW positions of the tile each.  The focus record of a position is a
+//    broadcast LDS read; the candidate's record of lane d at position u is the moving image's at
+//    u - d (right view: u + d), read from a mirrored span ring like the arm span ring: every record
+//    is written at slot i and i + RR, a tile's window of 63 + T records never wraps and a tile adds
+//    its T new records.  Candidates outside the row carry k_cost's sentinel record;
+//  * the first cost wave also stages: lanes < T fetch the raw inputs of a tile's new focus and
+//    moving records (census words, the gradients' gray bytes, the arm words of the weights) two
+//    steps before it finishes them (grad_finish, cost_grad_weights) and writes them to LDS.
+// Pipeline: step s stages tile s, computes the costs of tile s - 1 and scans tile s - 2, with ONE
+// workgroup barrier (after lgkmcnt(0)) at the end of every step: focus records and hand-over
+// tiles are double-buffered (written in step s, read in step s + 1, written again in step s + 2),
+// and the record ring holds RR = 63 + 2 T slots, the window of tile s - 1 plus the new records of
+// tile s.  Every role's loop has the same bounds (from nst) and one barrier per step.
+#ifndef SM_CB_HSC_NCW
+#define SM_CB_HSC_NCW 3   // cost waves per workgroup (a divisor of T).  Full resolution, same process
+                          // (profiles/fuse_cost_scan/abvar_fullres.txt): 2 -> 4.57-4.69 ms, 3 -> 4.33-4.61,
+                          // 4 (15 waves per CU at the same three workgroups) -> 9.0-9.5 ms
+#endif
+#ifndef SM_CB_HSC_PRIO
+#define SM_CB_HSC_PRIO 2   // s_setprio of the scan wave: the kernel alone is unchanged (4.59-4.62 ms) but the
+                           // pipelined step, where it shares the CUs with the other group's SGM passes, ran
+                           // 29.63-29.65 -> 28.89-28.92 ms (same file; 0: no priority)
+#endif
+__constant__ uint64_t c_exp_tab_cb[32] = SM_EXPF_TABLE;
+constexpr int HSC_T = SM_CB_T_SCAN_H;
+constexpr int HSC_NCW = SM_CB_HSC_NCW;
+constexpr int HSC_KP = HSC_T / HSC_NCW;      // positions of a tile per cost wave
+constexpr int HSC_RR = 63 + 2 * HSC_T;       // record ring slots (mirrored: 2 RR records)
+static_assert(HSC_T % HSC_NCW == 0, "the cost waves share a tile's positions evenly");
+// dynamic LDS in 4-byte words: the scan's rings and arm words (rounded up to 16 bytes), the record
+// ring as two planes ({census words[, bias]} uint4 and {gx, gy} uint2, or {gx, gy, bias, 0} uint4
+// with four census words), two sets of T focus records (two uint4 each), two hand-over tiles
+__host__ __device__ inline int hsc_base_words(int lag) { return (cbca_smem_words(lag, true, CB_SCAN) + 3) & ~3; }
+__host__ __device__ constexpr int hsc_rec_words(int cw) { return 2 * HSC_RR * (4 + (cw == 3 ? 2 : 4)); }
+__host__ __device__ inline int hsc_smem_words(int lag, int cw) {
+    return hsc_base_words(lag) + hsc_rec_words(cw) + 2 * HSC_T * 8 + 2 * HSC_T * 64;
+}
+size_t cbca_hsc_smem_bytes(int lag, int cwords) { return 4 * (size_t)hsc_smem_words(lag, cwords) + 8 * 32 + 4 * LUT_T_N; }
+
+typedef uint32_t hsc_u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t hsc_u3 __attribute__((ext_vector_type(3)));
+typedef uint32_t hsc_u2 __attribute__((ext_vector_type(2)));
+struct HscRaw {            // lane k < T: a tile's new focus (position j0 + k) and moving record, as fetched
+    hsc_u4 fc, mc;         // census words
+    GradRaw fg, mg;        // the gradients' gray bytes
+    uint32_t fah, fav;     // focus pixel's arm pairs (adaptive weights)
+};
+
+template <bool FULL, bool RV, int CW>
+__global__ __launch_bounds__(64 * (1 + HSC_NCW)) void k_cbca_hsc(const CbcaArgs a) {
+    extern __shared__ __align__(16) float hsc_smem[];
+    // static LDS (link-time addresses, see LdsExpTab): the 2^(i/32) table and the clamped 2 - e0 table
+    __shared__ uint64_t etab[32];
+    __shared__ float lutt[LUT_T_N];
+    constexpr int T = HSC_T, NCW = HSC_NCW, KP = HSC_KP, RR = HSC_RR, NTH = 64 * (1 + NCW);
+    using L_t = CbLine<true, CB_SCAN, FULL, false, RV, 0>;
+    static_assert(L_t::T == T && CbCfg<true, CB_SCAN>::PF == 1, "the scan wave runs the H scan's tiles, one ahead");
+    using Tile = typename L_t::Tile;
+    using RecB = typename std::conditional<CW == 3, hsc_u2, hsc_u4>::type;
+    const int blk = xcd_swizzle(blockIdx.x, gridDim.x);
+    const int tid = (int)threadIdx.x;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    L_t L;
+    const int nst = cbca_line_setup(L, a, blk, hsc_smem, wid == 0 ? 0xff : 0, tid, NTH);
+    const int lane = L.lane;
+    const int W = a.W, H = a.H, v = L.line, c64 = L.c64;
+    const int b = blk / (H * ((a.D + 63) / 64));
+    const size_t npix = (size_t)H * W;
+    const int fview = RV ? 1 : 0, mview = 1 - fview;   // focus image = the view's own, moving = the other
+    const uint8_t* grayF = a.gray + ((size_t)b * 2 + fview) * npix;
+    const uint8_t* grayM = a.gray + ((size_t)b * 2 + mview) * npix;
+    const hsc_u4* codeF = (const hsc_u4*)(a.code + ((size_t)b * 2 + fview) * npix + (size_t)v * W);
+    const hsc_u4* codeM = (const hsc_u4*)(a.code + ((size_t)b * 2 + mview) * npix + (size_t)v * W);
+    const uint32_t* armF = a.arms + ((size_t)b * 4 + fview * 2) * npix + (size_t)v * W;
+    const int icd = (int)a.census_default;
+    uint32_t* cw = (uint32_t*)hsc_smem + hsc_base_words(a.lag);
+    hsc_u4* recA = (hsc_u4*)cw;                      // [2 RR]
+    RecB* recB = (RecB*)(cw + 8 * RR);               // [2 RR]
+    hsc_u4* fA = (hsc_u4*)(cw + hsc_rec_words(CW));  // [2][T] census words
+    hsc_u4* fB = fA + 2 * T;                         // [2][T] {gx, gy, wa, wb}
+    float* hx = (float*)(fB + 2 * T);                // [2][T][64] hand-over tiles
+    if (tid < 32) etab[tid] = c_exp_tab_cb[tid];
+    for (int i = tid; i < LUT_T_N; i += NTH) lutt[i] = 2.0f - a.lut[min(i, icd)];   // (as k_cost builds it)
+    // (no barrier of their own: the tables' first readers are the cost waves in step 1, after the
+    // barrier that ends step 0 -- keep one between these writes and any earlier read)
+
+    // a moving record into ring slot i and its mirror; !valid: k_cost's out-of-range sentinel
+    auto put_moving = [&](int i, bool valid, const hsc_u4 mc, float2 g) __attribute__((always_inline)) {
+        const uint32_t gx = __float_as_uint(valid ? g.x : COST_OOR_GRAD), gy = __float_as_uint(valid ? g.y : COST_OOR_GRAD);
+        const uint32_t bias = valid ? 0u : (uint32_t)icd;
+        const hsc_u4 ra = {valid ? mc.x : 0u, valid ? mc.y : 0u, valid ? mc.z : 0u, CW == 3 ? bias : (valid ? mc.w : 0u)};
+        RecB rb;
+        if constexpr (CW == 3) rb = hsc_u2{gx, gy};
+        else rb = hsc_u4{gx, gy, bias, 0u};
+        recA[i] = ra;
+        recA[i + RR] = ra;
+        recB[i] = rb;
+        recB[i + RR] = rb;
+    };
+    // moving position of tile t's new record k: q0 + 63 + k with the window's first position
+    // q0 = t T + c64 (right view) / t T - c64 - 63 (left view)
+    auto new_q = [&](int t, int k) __attribute__((always_inline)) { return RV ? t * T + c64 + 63 + k : t * T - c64 + k; };
+    // the raw inputs of tile t's new records: unconditional loads at clamped positions
+    auto fetch = [&](HscRaw& r, int t) __attribute__((always_inline)) {
+        const int ln = min(lane, T - 1);
+        const int p = min(t * T + ln, W - 1);
+        const int qc = min(max(new_q(t, ln), 0), W - 1);
+        r.fc = codeF[p];
+        r.fg = grad_fetch(grayF, v, p, H, W);
+        r.fah = armF[p];
+        r.fav = armF[npix + p];
+        if constexpr (CW == 3) {   // (three words: an unused fourth register would be reused under the load)
+            const hsc_u3 m3 = *(const hsc_u3*)(codeM + qc);
+            r.mc = hsc_u4{m3.x, m3.y, m3.z, 0u};
+        } else {
+            r.mc = codeM[qc];
+        }
+        r.mg = grad_fetch(grayM, v, qc, H, W);
+    };
+    // tile t's records into LDS: focus set `buf`, ring slots wrw + 63 .. wrw + 62 + T (wrw = t T mod RR)
+    auto stage = [&](const HscRaw& r, int t, int wrw, int buf) __attribute__((always_inline)) {
+        if (lane < T) {
+            const int p = min(t * T + lane, W - 1);   // (positions past the row are never output)
+            const int q = new_q(t, lane);
+            const int qc = min(max(q, 0), W - 1);
+            const float2 fg = grad_finish(r.fg, v, p, H, W);
+            float2 wg = make_float2(1.f, 1.f);
+            if (a.grad_adaptive) wg = cost_grad_weights(r.fah, r.fav);
+            fA[buf * T + lane] = r.fc;
+            fB[buf * T + lane] = hsc_u4{__float_as_uint(fg.x), __float_as_uint(fg.y), __float_as_uint(wg.x), __float_as_uint(wg.y)};
+            int i = wrw + 63 + lane;   // < 2 RR
+            i = i >= RR ? i - RR : i;
+            put_moving(i, (unsigned)q < (unsigned)W, r.mc, grad_finish(r.mg, v, qc, H, W));
+        }
+    };
+    // the costs of positions cwi KP .. cwi KP + KP - 1 of tile t (window at ring slot wrc, focus
+    // set and hand-over tile `buf`)
+    const int cwi = wid - 1;
+    auto cost_tile = [&](auto fastc, int wrc, int buf) __attribute__((always_inline)) {
+        constexpr bool FAST = decltype(fastc)::value;
+        const int k0 = cwi * KP;
+        const int ro = wrc + k0 + (RV ? lane : 63 - lane);
+        const hsc_u4* ra = recA + ro;
+        const RecB* rb = recB + ro;
+        const hsc_u4* fa = fA + buf * T + k0;
+        const hsc_u4* fb = fB + buf * T + k0;
+        float* ho = hx + (buf * T + k0) * 64 + lane;
+#pragma unroll
+        for (int kk = 0; kk < KP; kk++) {
+            const hsc_u4 r0 = ra[kk];
+            uint2 gw;
+            uint32_t pc;
+            if constexpr (CW == 3) {
+                const hsc_u2 r1 = rb[kk];
+                gw = make_uint2(r1.x, r1.y);
+                pc = r0.w;
+            } else {
+                const hsc_u4 r1 = rb[kk];
+                gw = make_uint2(r1.x, r1.y);
+                pc = r1.z;
+            }
+            const hsc_u4 f0 = fa[kk], f1 = fb[kk];   // broadcast reads
+            ho[kk * 64] = cost_elem_nosel<CW, true, FAST>(make_uint4(r0.x, r0.y, r0.z, r0.w), gw, pc, f0.x, f0.y, f0.z, f0.w, __uint_as_float(f1.x),
+                                                          __uint_as_float(f1.y), __uint_as_float(f1.z), __uint_as_float(f1.w),
+                                                          a.grad_trunc, 1.0f, lutt, etab);
+        }
+    };
+    // FAST elements (sm_cost_elem.h): k_cost's rule per focus pixel, here for a wave's KP pixels
+    const bool fast_rows = v > 0 && v < H - 1 && a.grad_trunc >= 382.5f && a.grad_adaptive;
+    auto ring_adv = [](int w) __attribute__((always_inline)) { return w + T >= RR ? w + T - RR : w + T; };
+
+    const int NT = (nst + T - 1) / T;   // tiles of the line
+    Tile tq[2];
+    HscRaw rq[2];
+    int wrw = 0, wrc = 0;               // ring slot of the window of the next tile to stage / to compute
+    if (wid == 0) {
+        L.template load<2>(tq[0], 0);
+    } else if (wid == 1) {
+        if (lane < 63) {   // the first window's records before tile 0's own
+            const int q = (RV ? c64 : -c64 - 63) + lane;
+            const int qc = min(max(q, 0), W - 1);
+            put_moving(lane, (unsigned)q < (unsigned)W, codeM[qc], grad_finish(grad_fetch(grayM, v, qc, H, W), v, qc, H, W));
+        }
+        fetch(rq[0], 0);
+        fetch(rq[1], 1);
+    }
+    // Barriers: each role runs its own copy of the SAME loop -- trips of two steps from s0 = 0 while
+    // s0 < NT + 2, one barrier at the end of every step, nothing else leaves the loop -- so every
+    // wave passes 2 * ceil((NT + 2) / 2) barriers, whatever its role and however short the line; a
+    // step outside a role's tiles only skips that role's work.  (s0 is even: n is the parity of
+    // tiles s and s - 2, 1 - n that of tile s - 1.)
+    // the costs of tile s - 1 (cost waves)
+    auto cost_step = [&](int s, int n) __attribute__((always_inline)) {
+        const int tc = s - 1;
+        if (tc >= 0 && tc < NT) {
+            const int p0 = tc * T + cwi * KP;
+            if (fast_rows && p0 > 0 && p0 + KP - 1 < W - 1)
+                cost_tile(std::true_type{}, wrc, 1 - n);
+            else
+                cost_tile(std::false_type{}, wrc, 1 - n);
+            wrc = ring_adv(wrc);
+        }
+    };
+    if (wid == 0) {
+#if SM_CB_HSC_PRIO
+        __builtin_amdgcn_s_setprio(SM_CB_HSC_PRIO);
+#endif
+        for (int s0 = 0; s0 < NT + 2; s0 += 2) {
+            auto step = [&](auto nc) {
+                constexpr int n = decltype(nc)::value;
+                const int ts = s0 + n - 2;   // the scan of tile s - 2
+                if (ts >= 0 && ts < NT) {
+                    L.template load<2>(tq[1 - n], (ts + 1) * T);
+                    const float* hi = hx + n * T * 64 + lane;
+#pragma unroll
+                    for (int k = 0; k < T; k++) tq[n].x[k] = hi[k * 64];
+                    L.process(tq[n], ts * T);
+                }
+                nsv2_bar_lgkm();   // step s: tile s - 2 consumed
+            };
+            step(std::integral_constant<int, 0>{});
+            step(std::integral_constant<int, 1>{});
+        }
+    } else if (wid == 1) {
+        for (int s0 = 0; s0 < NT + 2; s0 += 2) {
+            auto step = [&](auto nc) {
+                constexpr int n = decltype(nc)::value;
+                const int s = s0 + n;
+                if (s < NT) {
+                    stage(rq[n], s, wrw, n);
+                    wrw = ring_adv(wrw);
+                }
+                fetch(rq[n], s + 2);   // (into the set just consumed: two steps ahead with two sets)
+                cost_step(s, n);
+                nsv2_bar_lgkm();   // step s: records of tile s and costs of tile s - 1 written
+            };
+            step(std::integral_constant<int, 0>{});
+            step(std::integral_constant<int, 1>{});
+        }
+    } else {
+        for (int s0 = 0; s0 < NT + 2; s0 += 2) {
+            cost_step(s0, 0);
+            nsv2_bar_lgkm();   // step s: costs of tile s - 1 written
+            cost_step(s0 + 1, 1);
+            nsv2_bar_lgkm();
+        }
+    }
+}
+
+template <bool FULL, bool RV>
+static void launch_hsc_cw(const CbcaArgs& a, dim3 grid, dim3 block, size_t shm, hipStream_t st) {
+    if (a.cwords == 3) hipLaunchKernelGGL((k_cbca_hsc<FULL, RV, 3>), grid, block, shm, st, a);
+    else hipLaunchKernelGGL((k_cbca_hsc<FULL, RV, 4>), grid, block, shm, st, a);
+}
+
+void launch_cbca_hsc(const CbcaArgs& a, int n, hipStream_t st) {
+    const int nchunks = (a.D + 63) / 64;
+    dim3 grid(a.H * nchunks * n), block(64 * (1 + HSC_NCW));
+    const size_t shm = 4 * (size_t)hsc_smem_words(a.lag, a.cwords);
+    const bool full = a.D % 64 == 0;
+    if (a.view == 0) {
+        if (full) launch_hsc_cw<true, false>(a, grid, block, shm, st);
+        else launch_hsc_cw<false, false>(a, grid, block, shm, st);
+    } else {
+        if (full) launch_hsc_cw<true, true>(a, grid, block, shm, st);
+        else launch_hsc_cw<false, true>(a, grid, block, shm, st);
+    }
 }
 
 template <bool HORIZ, int MODE, bool FULL, bool SCALE, bool RV, int LAGC = 0>

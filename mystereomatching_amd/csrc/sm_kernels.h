@@ -63,6 +63,14 @@ struct CbcaArgs {
                                 // has >= 2 lag + 64 rows of tail pad, and the volumes >= 8 rows)
     int div_safe;               // 1: every dividend of this launch's normalisation is 0 or >= 2^-110
                                 // (proven by the host, cbca_div_safe): the area division needs no check
+    // The first H scan that computes its censusGrad costs itself (launch_cbca_hsc): CostArgs'
+    // inputs of the select-free elements with lamG == 1 (cost_nosel_ok, >= 3 census words)
+    const ulonglong2* code;     // [n][2][H][W]
+    const uint8_t* gray;        // [n][2][H][W]
+    const float* lut;           // the context's exponent tables (CostArgs::lut)
+    float census_default, grad_trunc;
+    int grad_adaptive;
+    int cwords;                 // 32-bit census words in use: 3 or 4
 };
 constexpr int CBCA_VM_TAIL_ROWS = 8;   // volume tail pad in rows of W * D floats (fast V sweeps)
 
@@ -181,6 +189,10 @@ void launch_cost(const CostArgs& a, int method, int n, hipStream_t st);
 void launch_prep(const PrepArgs& a, int n, hipStream_t st);
 size_t prep_smem_bytes(int rv, int ru, int L_out);
 void launch_cbca(const CbcaArgs& a, bool horiz, int mode, int n, hipStream_t st);
+// the first H scan (CB_SCAN) of a view whose cost volume was not written: costs computed in the sweep
+void launch_cbca_hsc(const CbcaArgs& a, int n, hipStream_t st);
+size_t cbca_hsc_smem_bytes(int lag, int cwords);   // its LDS per workgroup (static tables included)
+bool cost_nosel_ok(float grad_trunc, float lam2, float census_default);   // the select-free cost elements apply
 void launch_scale(float* vm, size_t n, float w, hipStream_t st);
 void launch_sgm_path(const SgmArgs& a, int mode, int n, hipStream_t st);
 // Checkpointed path pairs (sm_sgm.hip, k_sgm_ck): CK_A sweeps the pair's first path and keeps

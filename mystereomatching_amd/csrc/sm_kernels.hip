@@ -16,6 +16,7 @@
 
 #include <type_traits>
 
+#include "sm_cost_elem.h"
 #include "sm_device.h"
 #include "sm_kernels.h"
 
@@ -230,25 +231,7 @@ __device__ __forceinline__ void prep_census_grad(const PrepArgs& a, const uint8_
 // wide image has 0, as the prep halo's reflection gave).  The cost kernel evaluates them from the
 // gray plane when it stages a row, so no gradient plane goes through HBM.
 __device__ __forceinline__ float2 grad_at(const uint8_t* G, int v, int u, int H, int W) {
-    const uint8_t* row = G + (size_t)v * W;
-    float gxv, gyv;
-    if (W == 1)
-        gxv = 0.f;
-    else if (u == 0)
-        gxv = (float)((int)row[1] - (int)row[0]);
-    else if (u == W - 1)
-        gxv = (float)((int)row[u] - (int)row[u - 1]);
-    else
-        gxv = 0.5f * (float)((int)row[u + 1] - (int)row[u - 1]);
-    if (H == 1)
-        gyv = 0.f;
-    else if (v == 0)
-        gyv = (float)((int)row[W + u] - (int)row[u]);
-    else if (v == H - 1)
-        gyv = (float)((int)row[u] - (int)row[u - W]);
-    else
-        gyv = 0.5f * (float)((int)row[W + u] - (int)row[u - W]);
-    return make_float2(gxv, gyv);
+    return grad_finish(grad_fetch(G, v, u, H, W), v, u, H, W);   // (sm_cost_elem.h)
 }
 
 // One arm walk over an LDS strip of arm-walk words (calHorVerDis, cpp:2959-3050): sp = the centre
@@ -889,52 +872,12 @@ constexpr int LUT_A_N = 129, LUT_B_N = 766;
 template <int CW>
 __host__ __device__ constexpr int cost_rec_u4() { return CW <= 2 ? 1 : 2; }
 
-// Select-free gradient elements (NOSEL = censusGrad with >= 3 census words and OORZ): an
-// out-of-range candidate's staged record carries gx = gy = 1e30 and a census count bias of
-// icd, so the element's own arithmetic yields the reference's out-of-range value without a
-// select: min(|f - 1e30|, T) = T per axis (T = grad_trunc, 500) makes G >= 0.999 T (the host
-// enables the path only when -0.999 T / lamG < -17.5, so e1 rounds away exactly as it does for
-// the reference's 707.1068), and popc + icd >= icd
-// picks LUT entry icd (the LUT holds 2 - expf(-C / lamCen) and is clamped at icd, so no min
-// is needed either).  The exponential's input is clamped at -100 instead of selecting 0 below
-// -17.5: expf_glibc_core is exact down to -103.9, and every value below 2^-25 leaves
-// fl(t - e) == t (see above).  Saves the range test, three selects and a min per element.
-constexpr int LUT_T_N = 260;   // >= 128 census bits + icd (<= 128) + 1
-// The out-of-range sentinel gradient (NOSEL): |f - S| for a real gradient f in [-255, 255] lies in
-// [S - 255, S + 255] = [295, 805]; with the truncation min(., T) the element's G is then >= 0.999
-// min(T, 295) (the host's NOSEL test), and unclamped (FAST below) G <= 677.5.
-constexpr float COST_OOR_GRAD = 550.0f;
-// FAST elements (NOSEL, lamG == 1, adaptive weights, T >= 382.5, focus pixel off the image border): the gradient
-// images are 0.5 (I[+1] - I[-1]) inside the image and full differences on its border rows and
-// columns (calGrad, cpp:271-350), so an interior focus pixel has |gx|, |gy| <= 127.5 and a
-// candidate in the same row |gx| <= 255, |gy| <= 127.5: |dx| <= 382.5 <= T and |dy| <= 255, the
-// truncation is the identity, and wa |dx| == |fl(wa dx)| (wa, wb > 0; round-to-nearest is
-// symmetric), so G = |fl(wa dx)| + |fl(wb dy)| takes one packed subtract, one packed multiply and
-// one add with both operands' abs modifiers.  With wa + wb = 1 (up to 2^-24), G <= 382.5 for real
-// candidates and <= 677.5 for the sentinel (unit weights could reach 1355), so -G >= -700 keeps expf_glibc_core's exponent field from wrapping without the -100
-// clamp (below -103.9 the core returns a double < 2^-149 that rounds to 0 or the least
-// subnormal, which fl(t - e) absorbs like the reference's exact value).  The census count
-// starts from the record's bias word and accumulates through three v_bcnt_u32_b32 (one chain).
+// The select-free elements (NOSEL = censusGrad with >= 3 census words and OORZ), their FAST form,
+// the sentinel record of an out-of-range candidate and the LDS table reads are in sm_cost_elem.h,
+// shared with the CBCA sweep that computes its own costs (k_cbca_hsc, sm_cbca.hip).
 #ifndef SM_COST_FAST
 #define SM_COST_FAST 1
 #endif
-// The cost kernel's LDS copy of the 2^(i/32) table sits in static LDS (a link-time address), so
-// its byte offset (ki % 32) * 8 is one SDWA shift with a byte-0 destination select
-// ((ki << 3) & 0xff) and the table's address goes into the ds_read's offset field.
-struct LdsExpTab {
-    const uint64_t* p;
-};
-__device__ __forceinline__ uint64_t exp_tab_at(const LdsExpTab& t, uint64_t ki) {
-    uint32_t off;
-    asm("v_lshlrev_b32_sdwa %0, 3, %1 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD"
-        : "=v"(off) : "v"((uint32_t)ki));
-    return *(const uint64_t*)((const char*)t.p + off);
-}
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
 
 // ND > 0: D == 64 * ND, the element loop fully unrolled (LDS and store offsets become immediates;
 // no loop counter, compare or pointer increments: 35 -> ~29 VALU per element at D = 256)
@@ -1001,13 +944,9 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
             float wa = 1.f, wb = 1.f;
             if (a.grad_adaptive) {
                 const uint32_t* planes = (const uint32_t*)a.arms + ((size_t)b * 2 + fview) * 2 * npix + (size_t)v * W + u;
-                const uint32_t ph = planes[0], pv = planes[npix];
-                float sH = (float)min(ph & 0xffffu, ph >> 16);
-                float sV = (float)min(pv & 0xffffu, pv >> 16);
-                if (sH == 0) sH = 1;
-                if (sV == 0) sV = 1;
-                wa = sH / (sH + sV);
-                wb = 1.0f - wa;
+                const float2 wg = cost_grad_weights(planes[0], planes[npix]);
+                wa = wg.x;
+                wb = wg.y;
             }
             fwa[i] = wa;
             fwb[i] = wb;
@@ -1082,7 +1021,6 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
             constexpr bool FAST = decltype(fastc)::value;
             const int q = mi + mbase;
             if constexpr (NOSEL) {
-                typedef float f2 __attribute__((ext_vector_type(2)));
                 const uint4 r0 = recA(mi);
                 uint32_t pc;
                 uint2 gw;
@@ -1094,24 +1032,9 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
                     pc = r1.z;
                     gw = make_uint2(r1.x, r1.y);
                 }
-                pc = bcnt_acc((uint32_t)cf.x ^ r0.x, pc);
-                pc = bcnt_acc((uint32_t)(cf.x >> 32) ^ r0.y, pc);
-                pc = bcnt_acc((uint32_t)cf.y ^ r0.z, pc);
-                if (CW == 4) pc = bcnt_acc((uint32_t)(cf.y >> 32) ^ r0.w, pc);
-                const f2 dv = f2{fx, fy} - f2{__uint_as_float(gw.x), __uint_as_float(gw.y)};
-                float g;
-                if constexpr (FAST) {
-                    const f2 tv = f2{wa, wb} * dv;
-                    g = fabsf(tv.x) + fabsf(tv.y);
-                } else {
-                    const f2 tv = f2{wa, wb} * f2{fminf(fabsf(dv.x), a.grad_trunc), fminf(fabsf(dv.y), a.grad_trunc)};
-                    g = tv.x + tv.y;
-                }
-                // (-fminf(g, 100) == fmaxf(-g, -100): both paths end in a negated conversion)
-                const float xg = LAM1 ? (FAST ? -g : -fminf(g, 100.0f)) : fmaxf(-g / a.lam2, -100.0f);
-                const float t = luta[pc];                       // fl(2 - expf(-min(pc, icd) / lamCen))
-                const float ex = expf_glibc_core(xg, LdsExpTab{etab});
-                const float res = t - ex;
+                const float res = cost_elem_nosel<CW, LAM1, FAST>(r0, gw, pc, (uint32_t)cf.x, (uint32_t)(cf.x >> 32),
+                                                                  (uint32_t)cf.y, (uint32_t)(cf.y >> 32), fx, fy, wa, wb,
+                                                                  a.grad_trunc, a.lam2, luta, etab);
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, res), ro, voff, soff,
                                                       SM_COST_STORE_AUX);
                 return;
@@ -1320,6 +1243,12 @@ static void launch_cost_z(const CostArgs& a, dim3 grid, dim3 block, size_t shm, 
         hipLaunchKernelGGL((k_cost<METHOD, LAM1, CW, false, OORZ>), grid, block, shm, st, a);
 }
 
+bool cost_nosel_ok(float grad_trunc, float lam2, float census_default) {
+    const float gmin = 0.999f * fminf(grad_trunc, COST_OOR_GRAD - 255.0f);
+    const float xg = lam2 == 1.0f ? -gmin : -gmin / lam2;
+    return xg < -17.5f && grad_trunc < 1e29f && (int)census_default <= 128 && (int)census_default >= 0;
+}
+
 template <int METHOD, bool LAM1, int CW>
 static void launch_cost_nw(const CostArgs& a, dim3 grid, dim3 block, size_t shm, hipStream_t st) {
     // select-free elements (NOSEL in k_cost): an out-of-range pair's G is at least
@@ -1327,10 +1256,8 @@ static void launch_cost_nw(const CostArgs& a, dim3 grid, dim3 block, size_t shm,
     // wa + fl(1 - wa) = 1 up to 2^-24), and its exponential
     // must still round away: xg = -G (lamG == 1) or -G / lamG below -17.5; the clamped
     // 2 - e0 table covers counts up to 128 + icd
-    const float gmin = 0.999f * fminf(a.grad_trunc, COST_OOR_GRAD - 255.0f);
-    const float xg = LAM1 ? -gmin : -gmin / a.lam2;
     if constexpr (METHOD == SM_M_CENSUS_GRAD && CW >= 3) {
-        if (xg < -17.5f && a.grad_trunc < 1e29f && (int)a.census_default <= 128 && (int)a.census_default >= 0)
+        if (cost_nosel_ok(a.grad_trunc, LAM1 ? 1.0f : a.lam2, a.census_default))
             return launch_cost_z<METHOD, LAM1, CW, true>(a, grid, block, shm, st);
     }
     launch_cost_z<METHOD, LAM1, CW, false>(a, grid, block, shm, st);

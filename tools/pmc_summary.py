@@ -26,6 +26,8 @@ def profile_name(sym: str, seen: dict) -> str:
         return "cbca_v_norm_scan"
     if "k_cbca_hn" in sym:
         return "cbca_h_norm"
+    if "k_cbca_hsc" in sym:
+        return "cbca_h_scan_cost"
     m = re.search(r"k_sgm_ck<\d+, (\d+),", sym)
     if m:
         mode = int(m.group(1))  # CK_A = 16, CK_B = 32, CK_MID = 64, SGM_LAST = 2

@@ -11,6 +11,8 @@
  *   sm_create          <- StereoMatching::StereoMatching (ctor)      stereoMatching.cpp:2058-2110
  *   sm_set_images      <- ctor image arguments I1_c,I2_c,I1_g,I2_g   stereoMatching.cpp:2063-2071
  *   sm_cost_calculate  <- StereoMatching::costCalculate              stereoMatching.cpp:945-1021
+ *                         (aggregators: cbca cpp:5585-5666, guideFilter cpp:4492-4516, NL cpp:4892-4917,
+ *                          FIF_Improve cpp:4707-4890 and its plain form FIF cpp:4541-4705)
  *   sm_solve_all       <- SolveAll(StereoMatching**&, PY_LVL, REG_LAMBDA)  stereoMatching.cpp:2142-2208
  *   sm_solve_all_pyr   <- the same with PY_LVL > 1 (one ctx per level)     stereoMatching.cpp:2142-2208
  *   sm_pyr_down        <- cv::pyrDown on the inputs                     main_.cpp:145-148
@@ -62,7 +64,17 @@ typedef enum sm_aggregation {
     SM_AGG_CBCA = 1,         /* "CBCA" (main:16; cpp:1002-1003) — default */
     SM_AGG_GF = 2,           /* "GF"  guideFilter (cpp:4492-4516), form chosen by gf_mode; sgm / WTA only */
     SM_AGG_NL = 3,           /* "NL"  non-local MST tree filter (cpp:4892-4917, NL/NLCCA.cpp:27-96) */
+    /* 4 is reserved (rejected by sm_create) */
+    SM_AGG_FIF = 5,          /* "FIF" full-image guided filter: four weighted sweeps over the volume, form chosen
+                              * by fif_mode (FIF_Improve cpp:4707-4890, FIF cpp:4541-4705) */
 } sm_aggregation;
+
+/* "FIF"'s two forms: */
+typedef enum sm_fif_mode {
+    SM_FIF_IMPROVE = 0,      /* FIF_Improve (cpp:4707-4890), what costCalculate calls (cpp:1010-1011): every sweep
+                              * step takes the minimum over d - 1, d, d + 1 of the previous pixel (+ Pn off d) */
+    SM_FIF_PLAIN = 1,        /* FIF (cpp:4541-4705): the previous pixel's cost at d only */
+} sm_fif_mode;
 
 /* guideFilter's two builds (stereoMatching.h:38 `//#define MY_GUIDE`): */
 typedef enum sm_gf_mode {
@@ -160,6 +172,10 @@ typedef struct sm_params {
                                   * keeps the cost-volume kernel.  1 = wherever eligible, 0 = never,
                                   * -1 (default) = wherever eligible (measured faster at every
                                   * bench shape, Teddy to full resolution) */
+    /* aggregation "FIF" (read only with aggregation = SM_AGG_FIF) */
+    int32_t fif_mode;            /* sm_fif_mode: SM_FIF_IMPROVE (default) or SM_FIF_PLAIN */
+    float fif_eps;               /* eps = 0.08 (cpp:4713): weights exp(-|dI|^2 / eps^2) on I / 255; must be > 0 */
+    float fif_pn;                /* Pn = 2 (cpp:4714): penalty of the d +/- 1 neighbours (FIF_Improve); >= +0 */
 } sm_params;
 
 typedef struct sm_ctx sm_ctx;

@@ -337,6 +337,9 @@ class StereoMatching {
     // `#define MY_GUIDE` (h:38, commented out in the shipped build) as a switch: false = GF runs
     // cv::ximgproc::guidedFilter (cpp:4513), true = guideFilterCore_matlab (cpp:4509)
     inline static bool gf_my_guide = false;
+    // costCalculate's "FIF" branch calls FIF_Improve (cpp:1010-1012, `//FIF();` commented out):
+    // true selects the plain form FIF (cpp:4541-4705) instead
+    inline static bool fif_plain = false;
 
     struct Parameters {  // StereoMatching::Parameters (h:85-351), the fields the hot path reads
         int numDisparities, rows, cols;
@@ -487,13 +490,15 @@ class StereoMatching {
                         : costcalculation == "AD"       ? SM_COST_AD
                                                         : -1;
         if (p.cost_method < 0) throw std::invalid_argument("unsupported costcalculation: " + costcalculation);
-        if (aggregation != "CBCA" && aggregation != "GF" && aggregation != "NL" && !aggregation.empty())
+        if (aggregation != "CBCA" && aggregation != "GF" && aggregation != "NL" && aggregation != "FIF" &&
+            !aggregation.empty())
             throw std::invalid_argument("unsupported aggregation: " + aggregation);
         if (optimization != "sgm" && optimization != "so" && !optimization.empty())
             throw std::invalid_argument("unsupported optimization: " + optimization);
         p.aggregation = aggregation == "CBCA" ? SM_AGG_CBCA
                         : aggregation == "GF" ? SM_AGG_GF
                         : aggregation == "NL" ? SM_AGG_NL
+                        : aggregation == "FIF" ? SM_AGG_FIF
                                               : SM_AGG_NONE;
         p.optimization = optimization == "sgm" ? SM_OPT_SGM : (optimization == "so" ? SM_OPT_SO : SM_OPT_WTA);
         p.census_ring = param.censusFunc == 3;
@@ -518,6 +523,7 @@ class StereoMatching {
         p.do_proper_ipol = Do_properIpol ? 1 : 0;
         p.do_last_median_blur = Do_lastMedianBlur ? 1 : 0;
         p.gf_mode = gf_my_guide ? SM_GF_MY_GUIDE : SM_GF_XIMGPROC;
+        p.fif_mode = fif_plain ? SM_FIF_PLAIN : SM_FIF_IMPROVE;
         p.lr_consis = Do_LRConsis ? 1 : 0;
         check(sm_create(&ctx_, &p, hip_device), "sm_create");
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");

@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(_HERE, "libsm_hip.so")
 
 SM_OK, SM_EINVAL, SM_ENOMEM, SM_EHIP, SM_ESTATE = 0, 1, 2, 3, 4
 COST_METHODS = {"censusGrad": 0, "Census": 1, "ADCensus": 2, "AD": 3}
-AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3}
+AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3, "FIF": 5}   # 4 is reserved
+FIF_IMPROVE, FIF_PLAIN = 0, 1
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -44,6 +45,7 @@ class sm_params(C.Structure):
         ("lr_consis", C.c_int32),
         ("placement_trials", C.c_int32),
         ("fuse_cost_scan", C.c_int32),
+        ("fif_mode", C.c_int32), ("fif_eps", C.c_float), ("fif_pn", C.c_float),
     ]
 
 

@@ -78,6 +78,9 @@ struct sm_ctx {
     float* gfc_ab = nullptr;
     double* gfc_img = nullptr;
     float* gfc_pix = nullptr;
+    // aggregation "FIF": the scratch volume A (and c1 / T without the SGM sum to reuse), weight planes
+    float* fif_s = nullptr;     // [1 (+1 without acc)][cap][nvol]
+    float* fif_w = nullptr;     // [2][cap][npix] wh, wv of the view being filtered
     // aggregation "NL": median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -269,7 +272,14 @@ sm_status validate(const sm_params& p, std::string& why) {
     if (p.rows > 65535) return bad("rows must be <= 65535");
     if (p.num_disparities < 1 || p.num_disparities > 1024) return bad("num_disparities must be in [1, 1024]");
     if (p.cost_method < 0 || p.cost_method > 3) return bad("unknown cost_method");
-    if (p.aggregation < 0 || p.aggregation > 3) return bad("unknown aggregation");
+    if (p.aggregation < 0 || p.aggregation > SM_AGG_FIF || p.aggregation == 4) return bad("unknown aggregation");   // (4: reserved)
+    if (p.aggregation == SM_AGG_FIF) {
+        if (p.fif_mode != SM_FIF_IMPROVE && p.fif_mode != SM_FIF_PLAIN)
+            return bad("fif_mode must be 0 (FIF_Improve) or 1 (FIF, the plain form)");
+        if (!(p.fif_eps > 0)) return bad("fif_eps must be > 0");
+        // the sweeps keep every cost >= +0 (as SGM's and so's minima assume) only with Pn >= +0
+        if (!nonneg(p.fif_pn)) return bad("fif_pn must be >= +0");
+    }
     if (p.aggregation == SM_AGG_GF) {
         if (p.gf_mode != SM_GF_XIMGPROC && p.gf_mode != SM_GF_MY_GUIDE)
             return bad("gf_mode must be 0 (ximgproc::guidedFilter) or 1 (MY_GUIDE)");
@@ -382,7 +392,7 @@ void free_all(sm_ctx* c) {
                     c->disp1, c->disp_tmp, c->dummy, c->flags, c->flags1, c->px, c->so_trace, c->so_cidx,
                     c->gf_s, c->gf_planes, c->gf_pix, c->gfc_rs, c->gfc_ab, c->gfc_img, c->gfc_pix, c->nl_med, c->nl_ew, c->nl_ints, c->nl_rec,
                     c->nl_table, c->nl_val, c->nl_oup, c->nl_ofin, c->nl_par, c->nl_best, c->nl_mst, c->nl_adj, c->nl_walk,
-                    c->nl_offs, c->luts, c->nl_vc, c->nl_fl};
+                    c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -793,11 +803,60 @@ sm_status run_nl(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w, Bufs*
 #define SM_FUSE_SOLVE_ALL 1   // sm_run: SolveAll's scaling in the GF / NL output stores (tuning switch)
 #endif
 
-// aggregation other than CBCA: GF on every view (num = Do_refine ? 2 : 1, cpp:4499), NL on vm[0]
+// FIF_Improve / FIF on one view (cpp:4707-4890, 4541-4705; sm_fif.hip): the view's weight planes,
+// then H forward (vm -> c1), H backward (vm, c1 -> A), V forward (A -> T), V backward (A, T -> vm).
+// c1 and T share one scratch volume (the SGM sum where there is one), A has its own; both are
+// the group's own pairs' slices, so groups on different streams never share scratch.
+sm_status run_fif(sm_ctx* c, int n, int view, const Bufs& B, bool solve_all, float w) {
+    const sm_params& p = c->p;
+    const size_t off = (size_t)(B.vm0 - c->vm0) / c->nvol, cap = c->cap, nv = c->nvol, np = c->npix;
+    float* vm = view == 0 ? B.vm0 : B.vm1;
+    float* s0 = (c->acc ? c->acc : c->fif_s + cap * nv) + off * nv;   // c1, then T
+    float* s1 = c->fif_s + off * nv;                                  // A
+    sm::FifArgs a{};
+    a.bgr = B.bgr + (size_t)view * np * 3;   // I_c[view] (cpp:4718)
+    a.bgr_pair_stride = 2 * np * 3;
+    a.wh = c->fif_w + off * np;
+    a.wv = c->fif_w + (cap + off) * np;
+    a.eps = p.fif_eps;
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.plain = p.fif_mode == SM_FIF_PLAIN;
+    a.pn = p.fif_pn;
+    a.scale = w;
+    const char* sfx = view == 0 ? "" : "_r";
+    auto nm = [&](const char* base) { return std::string(base) + sfx; };
+    sm_status s = timed(c, nm("fif_weights").c_str(), (double)n * np * (3 + 8), [&] { sm::launch_fif_weights(a, n, c->st); });
+    if (s) return s;
+    struct Pass { const char* name; const float* in; const float* fw; float* out; int vert, second; };
+    const Pass passes[4] = {{"fif_h_fwd", vm, nullptr, s0, 0, 0},
+                            {"fif_h_bwd", vm, s0, s1, 0, 1},
+                            {"fif_v_fwd", s1, nullptr, s0, 1, 0},
+                            {"fif_v_bwd", s1, s0, vm, 1, 1}};
+    for (int i = 0; i < 4; i++) {
+        const Pass& ps = passes[i];
+        a.in = ps.in;
+        a.fw = ps.fw;
+        a.out = ps.out;
+        a.vert = ps.vert;
+        a.second = ps.second;
+        a.solve_all = i == 3 && solve_all;   // SolveAll's 0 + w q in the last sweep's store
+        // forward: read one volume, write one; backward: read two, write one (+ the weight plane)
+        const double bytes = (double)n * nv * (ps.second ? 12.0 : 8.0) + (double)n * np * 4;
+        if ((s = timed(c, nm(ps.name).c_str(), bytes, [&] { sm::launch_fif_sweep(a, n, c->st); }))) return s;
+    }
+    return SM_OK;
+}
+
+// aggregation other than CBCA: GF and FIF on every view (num = Do_refine ? 2 : 1, cpp:4499, 4709-4711),
+// NL on vm[0]
 sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false, float w = 1.f) {
     sm_status s = SM_OK;
     if (c->p.aggregation == SM_AGG_GF)
         for (int v = 0; v < n_views(c->p) && !s; v++) s = run_gf(c, n, v, B, solve_all, w);
+    if (c->p.aggregation == SM_AGG_FIF)
+        for (int v = 0; v < n_views(c->p) && !s; v++) s = run_fif(c, n, v, B, solve_all, w);
     if (c->p.aggregation == SM_AGG_NL) s = run_nl(c, n, B, solve_all, w);
     return s;
 }
@@ -827,7 +886,10 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
         a.cor_thres = p.sgm_cor_dif_thres;
         a.redu = p.sgm_redu_coeff;
         a.keep_final = p.keep_final_volume;
-        a.signed_costs = p.aggregation == SM_AGG_GF;   // the guided filter's output can be < 0
+        // the guided filter's output can be < 0.  FIF's cannot (so it stays false there, and "so"
+        // applies too): with costs and weights >= +0 rounding is monotone, so c1, c2 >= vm, hence
+        // fl(c1 + c2) >= vm and A = fl(fl(c1 + c2) - vm) >= +0; the vertical pass likewise
+        a.signed_costs = p.aggregation == SM_AGG_GF;
         int first = 0;   // first path left to the plain sweeps
         if (B.ck) {
             // checkpointed pairs (0, 1) and (2, 3): 4 + 8 + 4 + 8 B per element (+ 4 / S for
@@ -1068,6 +1130,9 @@ void sm_params_default(sm_params* p, int32_t max_disp, int32_t rows, int32_t col
     p->nl_sigma = 0.1;          // NLCCA::aggreCV (NL/NLCCA.cpp:33)
     p->lr_consis = 1;           // Do_LRConsis (h:72)
     p->placement_trials = -1;   // auto (see sm_capi.h)
+    p->fif_mode = SM_FIF_IMPROVE;   // costCalculate calls FIF_Improve (cpp:1010-1012)
+    p->fif_eps = 0.08f;         // cpp:4713
+    p->fif_pn = 2.0f;           // cpp:4714
 }
 
 const char* sm_status_string(sm_status s) {
@@ -1172,6 +1237,10 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         if ((s = dalloc(c, &c->gf_s, (c->acc ? 3 : 4) * cap * c->nvol))) return s;
         if ((s = dalloc(c, &c->gf_planes, cap * 10 * c->npix))) return s;
         if ((s = dalloc(c, &c->gf_pix, cap * c->npix))) return s;
+    }
+    if (p->aggregation == SM_AGG_FIF) {
+        if ((s = dalloc(c, &c->fif_s, (c->acc ? 1 : 2) * cap * c->nvol))) return s;
+        if ((s = dalloc(c, &c->fif_w, 2 * cap * c->npix))) return s;
     }
     if (p->aggregation == SM_AGG_NL) {
         const size_t ne = (size_t)p->rows * (p->cols - 1) + (size_t)(p->rows - 1) * p->cols;
@@ -1633,8 +1702,9 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
         for (int v = 0; v < n_views(c->p) && !s_out && !pipe; v++) {
             if (c->p.aggregation == SM_AGG_CBCA && c->p.cbca_iterations > 0)
                 s_out = run_cbca(c, m2, v, true, w, B);   // SolveAll fused into the last pass
-            else if (!SM_FUSE_SOLVE_ALL || !(c->p.aggregation == SM_AGG_GF || (c->p.aggregation == SM_AGG_NL && v == 0)))
-                s_out = run_scale(c, m2, v, w, B);      // (GF and NL's vm[0]: fused above)
+            else if (!SM_FUSE_SOLVE_ALL || !(c->p.aggregation == SM_AGG_GF || c->p.aggregation == SM_AGG_FIF ||
+                                             (c->p.aggregation == SM_AGG_NL && v == 0)))
+                s_out = run_scale(c, m2, v, w, B);      // (GF, FIF and NL's vm[0]: fused above)
         }
         if (s_out) break;
         // the maps are written from here on: an asynchronous copy of the previous run's maps

@@ -131,6 +131,28 @@ struct GfCvArgs {               // guided filter, ximgproc form (sm_gf_cv.hip); 
 };
 void launch_gf_cv(const GfCvArgs& a, int n, hipStream_t st);
 
+struct FifArgs {                // full-image guided filter "FIF" (sm_fif.hip); pair-relative bases
+    // k_fif_weights: the view's colour image -> the weight planes
+    const uint8_t* bgr;         // the view's colour image of pair 0
+    size_t bgr_pair_stride;     // bytes between pairs
+    float* wh;                  // [n][H][W] weight between (v, u) and (v, u + 1)
+    float* wv;                  // [n][H][W] weight between (v, u) and (v + 1, u)
+    float eps;                  // 0.08f (cpp:4713)
+    // one sweep (launch_fif_sweep); wh (horizontal) / wv (vertical) are read
+    const float* in;            // [n][H][W][D] the sweep's `add` volume: vm (horizontal) or A (vertical)
+    const float* fw;            // backward sweeps: the forward sweep's result (c1 / T)
+    float* out;                 // forward: c1 / T; backward: (fw + L) - in
+    int H, W, D;
+    int vert;                   // 0: lines are rows, 1: lines are columns
+    int second;                 // 0: forward sweep, 1: backward sweep + combination
+    int plain;                  // 1: FIF (cpp:4541-4705), 0: FIF_Improve (cpp:4707-4890)
+    float pn;                   // Pn = 2 (cpp:4714)
+    int solve_all;              // 1: a backward sweep's output is SolveAll's `0 + w * q` (cpp:2189-2201)
+    float scale;
+};
+void launch_fif_weights(const FifArgs& a, int n, hipStream_t st);
+void launch_fif_sweep(const FifArgs& a, int n, hipStream_t st);
+
 struct NlArgs {                 // non-local tree filter (sm_nl.hip); node ids = pair * H W + pixel
     const int4* rec;            // path nodes, each path bottom -> top: {x, meta, child weights, parent}
                                 //   meta = nchild | (heavy + 1) << 3 | child directions << 6 (2 bits

@@ -39,6 +39,9 @@ class StereoMatching:
     # `#define MY_GUIDE` (h:38, commented out in the shipped build): guideFilter's form, False =
     # cv::ximgproc::guidedFilter (cpp:4513), True = guideFilterCore_matlab (cpp:4509)
     MY_GUIDE = False
+    # costCalculate's "FIF" branch calls FIF_Improve (cpp:1010-1012, `//FIF();` commented out):
+    # True selects the plain form FIF (cpp:4541-4705) instead
+    FIF_PLAIN = False
     Do_regionVote = True
     Do_properIpol = True
     Do_lastMedianBlur = True
@@ -80,7 +83,7 @@ class StereoMatching:
         def to_c(self, cost: str, aggregation: str, optimization: str, batch: int = 1,
                  compute_right_view: bool = False, keep_final_volume: bool = False,
                  do_refine: bool = False, switches=(True, True, True), my_guide: bool = False,
-                 lr_consis: bool = True) -> _capi.sm_params:
+                 lr_consis: bool = True, fif_plain: bool = False) -> _capi.sm_params:
             if self.censusFunc not in (0, 3):
                 raise ValueError("censusFunc must be 0 (plain census) or 3 (census + ring bits)")
             p = _capi.default_params(self.numDisparities - 1, self.rows, self.cols)
@@ -109,6 +112,7 @@ class StereoMatching:
             p.rv_ratio, p.rv_s = float(self.rv_ratio), int(self.rv_s)
             p.do_region_vote, p.do_proper_ipol, p.do_last_median_blur = (int(x) for x in switches)
             p.gf_mode = 1 if my_guide else 0
+            p.fif_mode = _capi.FIF_PLAIN if fif_plain else _capi.FIF_IMPROVE
             p.lr_consis = int(lr_consis)
             return p
 
@@ -135,6 +139,7 @@ class StereoMatching:
         if self.Do_refine and not self.Do_LRConsis:
             raise ValueError("Do_refine needs Do_LRConsis (refine() starts with the LR check, cpp:1364)")
         p = param.to_c(self.costcalculation, self.aggregation, self.optimization, my_guide=self.MY_GUIDE,
+                       fif_plain=self.FIF_PLAIN,
                        compute_right_view=self.Do_LRConsis and self.Do_refine,
                        keep_final_volume=keep_final_volume, do_refine=self.Do_refine, lr_consis=self.Do_LRConsis,
                        switches=(self.Do_regionVote, self.Do_properIpol, self.Do_lastMedianBlur))

@@ -12,7 +12,9 @@
  *   sm_set_images      <- ctor image arguments I1_c,I2_c,I1_g,I2_g   stereoMatching.cpp:2063-2071
  *   sm_cost_calculate  <- StereoMatching::costCalculate              stereoMatching.cpp:945-1021
  *                         (aggregators: cbca cpp:5585-5666, guideFilter cpp:4492-4516, NL cpp:4892-4917,
- *                          FIF_Improve cpp:4707-4890 and its plain form FIF cpp:4541-4705)
+ *                          FIF_Improve cpp:4707-4890 and its plain form FIF cpp:4541-4705,
+ *                          AWS cpp:5692-5801 without JBF_STANDARD, h:1305-1350, 1472-1493, 1533-1548)
+ *   sm_aws_config      <- AWS()'s local constants W_V_AWS, W_U_AWS (cpp:5715) and r_c (h:1478)
  *   sm_solve_all       <- SolveAll(StereoMatching**&, PY_LVL, REG_LAMBDA)  stereoMatching.cpp:2142-2208
  *   sm_solve_all_pyr   <- the same with PY_LVL > 1 (one ctx per level)     stereoMatching.cpp:2142-2208
  *   sm_pyr_down        <- cv::pyrDown on the inputs                     main_.cpp:145-148
@@ -67,6 +69,10 @@ typedef enum sm_aggregation {
     /* 4 is reserved (rejected by sm_create) */
     SM_AGG_FIF = 5,          /* "FIF" full-image guided filter: four weighted sweeps over the volume, form chosen
                               * by fif_mode (FIF_Improve cpp:4707-4890, FIF cpp:4541-4705) */
+    /* 6 is reserved (rejected by sm_create) */
+    SM_AGG_AWS = 7,          /* "AWS" adaptive support weights over a 35 x 35 window (cpp:5692-5801, the branch
+                              * without JBF_STANDARD); window and gamma_c: sm_aws_config.  The Lab planes are
+                              * OpenCV's 8-bit BGR2Lab restated (parity unpinned) */
 } sm_aggregation;
 
 /* "FIF"'s two forms: */
@@ -281,7 +287,18 @@ SM_API sm_status sm_profile_reset(sm_ctx* ctx);
 SM_API sm_status sm_cal_err(const int16_t* disp, const float* gt, const uint8_t* mask, int32_t rows, int32_t cols,
                             float thres, float* pbm, float* rms);
 
+/* "AWS"'s constants, function-local in the reference (W_V_AWS = W_U_AWS = 17, cpp:5715; r_c = 5, h:1478):
+ * each radius in [0, 17], gamma_c finite and > 0.  Defaults 17, 17, 5.  Applies from the next
+ * sm_cost_calculate / sm_run (buffers are sized for radius 17 at sm_create).  SM_EINVAL, with the
+ * argument named in sm_last_error, on a bad value or a context whose aggregation is not SM_AGG_AWS. */
+SM_API sm_status sm_aws_config(sm_ctx* ctx, int32_t radius_v, int32_t radius_u, float gamma_c);
+
 /* Diagnostics used by the parity tests. */
+/* "AWS": OpenCV's 8-bit BGR2Lab on the host (no device needed) with the tables the kernels use:
+ * npix packed BGR pixels -> npix packed (L, a, b); and the H x W x 3 plane the device computed for
+ * pair 0's image `view` in the last sm_cost_calculate / sm_run. */
+SM_API void sm_bgr2lab_host(const uint8_t* bgr, size_t npix, uint8_t* lab);
+SM_API sm_status sm_get_aws_lab(sm_ctx* ctx, int32_t view, uint8_t* dst);
 SM_API float sm_expf_host(float x);   /* the device expf algorithm, evaluated on the host */
 /* Device expf over the float bit patterns [first_bits, first_bits + n) into host out[n]. */
 SM_API sm_status sm_expf_device_range(sm_ctx* ctx, uint32_t first_bits, uint32_t n, float* out);

@@ -340,6 +340,10 @@ class StereoMatching {
     // costCalculate's "FIF" branch calls FIF_Improve (cpp:1010-1012, `//FIF();` commented out):
     // true selects the plain form FIF (cpp:4541-4705) instead
     inline static bool fif_plain = false;
+    // AWS()'s function-local constants W_V_AWS, W_U_AWS (cpp:5715) and r_c (h:1478), read with
+    // aggregation == "AWS" (sm_aws_config: radii in [0, 17], gamma_c > 0)
+    inline static int aws_radius_v = 17, aws_radius_u = 17;
+    inline static float aws_gamma_c = 5.0f;
 
     struct Parameters {  // StereoMatching::Parameters (h:85-351), the fields the hot path reads
         int numDisparities, rows, cols;
@@ -491,7 +495,7 @@ class StereoMatching {
                                                         : -1;
         if (p.cost_method < 0) throw std::invalid_argument("unsupported costcalculation: " + costcalculation);
         if (aggregation != "CBCA" && aggregation != "GF" && aggregation != "NL" && aggregation != "FIF" &&
-            !aggregation.empty())
+            aggregation != "AWS" && !aggregation.empty())
             throw std::invalid_argument("unsupported aggregation: " + aggregation);
         if (optimization != "sgm" && optimization != "so" && !optimization.empty())
             throw std::invalid_argument("unsupported optimization: " + optimization);
@@ -499,6 +503,7 @@ class StereoMatching {
                         : aggregation == "GF" ? SM_AGG_GF
                         : aggregation == "NL" ? SM_AGG_NL
                         : aggregation == "FIF" ? SM_AGG_FIF
+                        : aggregation == "AWS" ? SM_AGG_AWS
                                               : SM_AGG_NONE;
         p.optimization = optimization == "sgm" ? SM_OPT_SGM : (optimization == "so" ? SM_OPT_SO : SM_OPT_WTA);
         p.census_ring = param.censusFunc == 3;
@@ -526,6 +531,7 @@ class StereoMatching {
         p.fif_mode = fif_plain ? SM_FIF_PLAIN : SM_FIF_IMPROVE;
         p.lr_consis = Do_LRConsis ? 1 : 0;
         check(sm_create(&ctx_, &p, hip_device), "sm_create");
+        if (aggregation == "AWS") check(sm_aws_config(ctx_, aws_radius_v, aws_radius_u, aws_gamma_c), "sm_aws_config");
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }
     void check(sm_status s, const char* what) {

@@ -13,8 +13,9 @@ LIB_PATH = os.path.join(_HERE, "libsm_hip.so")
 
 SM_OK, SM_EINVAL, SM_ENOMEM, SM_EHIP, SM_ESTATE = 0, 1, 2, 3, 4
 COST_METHODS = {"censusGrad": 0, "Census": 1, "ADCensus": 2, "AD": 3}
-AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3, "FIF": 5}   # 4 is reserved
+AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3, "FIF": 5, "AWS": 7}   # 4 and 6 are reserved
 FIF_IMPROVE, FIF_PLAIN = 0, 1
+AWS_DEFAULTS = (17, 17, 5.0)   # radius_v, radius_u, gamma_c (sm_aws_config)
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -93,6 +94,9 @@ SIGNATURES = [
     ("sm_div_area_check", C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     ("sm_copy_ceiling", C.c_int, [_P, C.c_uint64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("sm_get_census", C.c_int, [_P, C.c_int32, _P]),
+    ("sm_aws_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_float]),
+    ("sm_bgr2lab_host", None, [_P, C.c_size_t, _P]),
+    ("sm_get_aws_lab", C.c_int, [_P, C.c_int32, _P]),
 ]
 
 _lib = None

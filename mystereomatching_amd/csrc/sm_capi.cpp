@@ -81,6 +81,15 @@ struct sm_ctx {
     // aggregation "FIF": the scratch volume A (and c1 / T without the SGM sum to reuse), weight planes
     float* fif_s = nullptr;     // [1 (+1 without acc)][cap][nvol]
     float* fif_w = nullptr;     // [2][cap][npix] wh, wv of the view being filtered
+    // aggregation "AWS": the window and gamma_c (sm_aws_config), the Lab tables and planes, the raw
+    // copies of the aggregated volumes, and one weight band per stream a group can run on
+    int aws_rv = sm::AWS_MAX_R, aws_ru = sm::AWS_MAX_R;
+    float aws_gamma = 5.0f;
+    uint16_t* aws_tab = nullptr;   // gam[256] | cb[3072]
+    uint8_t* aws_lab = nullptr;    // [cap][2][npix][3]
+    float* aws_raw = nullptr;      // [views][cap][nvol]
+    float* aws_band[4] = {nullptr, nullptr, nullptr, nullptr};   // each [2][aws_band_rows][S][W]
+    int aws_band_rows = 0;
     // aggregation "NL": median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -272,7 +281,12 @@ sm_status validate(const sm_params& p, std::string& why) {
     if (p.rows > 65535) return bad("rows must be <= 65535");
     if (p.num_disparities < 1 || p.num_disparities > 1024) return bad("num_disparities must be in [1, 1024]");
     if (p.cost_method < 0 || p.cost_method > 3) return bad("unknown cost_method");
-    if (p.aggregation < 0 || p.aggregation > SM_AGG_FIF || p.aggregation == 4) return bad("unknown aggregation");   // (4: reserved)
+    if (p.aggregation < 0 || p.aggregation > SM_AGG_AWS || p.aggregation == 4 || p.aggregation == 6)
+        return bad("unknown aggregation");   // (4, 6: reserved)
+    if (p.aggregation == SM_AGG_AWS) {   // the kernels' 32-bit offsets inside a volume row and a weight row
+        if (p.cols > (1 << 21) || (long long)p.cols * p.num_disparities >= (1LL << 29))
+            return bad("aggregation AWS needs cols <= 2^21 and cols * num_disparities < 2^29");
+    }
     if (p.aggregation == SM_AGG_FIF) {
         if (p.fif_mode != SM_FIF_IMPROVE && p.fif_mode != SM_FIF_PLAIN)
             return bad("fif_mode must be 0 (FIF_Improve) or 1 (FIF, the plain form)");
@@ -392,7 +406,8 @@ void free_all(sm_ctx* c) {
                     c->disp1, c->disp_tmp, c->dummy, c->flags, c->flags1, c->px, c->so_trace, c->so_cidx,
                     c->gf_s, c->gf_planes, c->gf_pix, c->gfc_rs, c->gfc_ab, c->gfc_img, c->gfc_pix, c->nl_med, c->nl_ew, c->nl_ints, c->nl_rec,
                     c->nl_table, c->nl_val, c->nl_oup, c->nl_ofin, c->nl_par, c->nl_best, c->nl_mst, c->nl_adj, c->nl_walk,
-                    c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w};
+                    c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w,
+                    c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3]};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -849,7 +864,100 @@ sm_status run_fif(sm_ctx* c, int n, int view, const Bufs& B, bool solve_all, flo
     return SM_OK;
 }
 
-// aggregation other than CBCA: GF and FIF on every view (num = Do_refine ? 2 : 1, cpp:4499, 4709-4711),
+// The 8-bit BGR2Lab tables (OpenCV's fixed-point path, restated: PARITY UNPINNED), gam | cb:
+//   gam[i] = round(255 * 8 * g(i / 255)), g the inverse sRGB curve;  cb[i] = round(32768 * f(i / (255 * 8)))
+const uint16_t* aws_tables() {
+    static const std::vector<uint16_t> tab = [] {
+        std::vector<uint16_t> t(sm::AWS_GAM_N + sm::AWS_CB_N);
+        for (int i = 0; i < sm::AWS_GAM_N; i++) {
+            const double x = i / 255.0;
+            const double g = x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4);
+            t[i] = (uint16_t)lrint(255.0 * 8.0 * g);
+        }
+        for (int i = 0; i < sm::AWS_CB_N; i++) {
+            const double x = i / (255.0 * 8.0);
+            const double f = x < 0.008856 ? 7.787 * x + 0.13793103448275862 : cbrt(x);
+            t[sm::AWS_GAM_N + i] = (uint16_t)lrint(32768.0 * f);
+        }
+        return t;
+    }();
+    return tab.data();
+}
+
+// The weight band of one stream: at most this many bytes, whatever the image height or the batch
+// (both images' weights of as many image rows as fit; at least one row).
+constexpr size_t AWS_BAND_BYTES = (size_t)256 << 20;
+
+// One band per stream of the schedule (sm_create, sm_set_schedule); a band is never freed or
+// resized before sm_destroy.
+sm_status aws_alloc_bands(sm_ctx* c) {
+    if (c->p.aggregation != SM_AGG_AWS) return SM_OK;
+    const size_t smax = (size_t)(2 * sm::AWS_MAX_R + 1) * (2 * sm::AWS_MAX_R + 1);
+    const size_t row_floats = 2 * smax * c->p.cols;
+    for (int i = 0; i < c->nstreams && i < 4; i++) {
+        if (c->aws_band[i]) continue;
+        // (+ 64 floats of slack past the last row)
+        sm_status s = dalloc(c, &c->aws_band[i], (size_t)c->aws_band_rows * row_floats + 64);
+        if (s) return s;
+    }
+    return SM_OK;
+}
+
+// AWS on every view of the group (cpp:5711-5792; sm_aws.hip): both images' Lab planes, a raw copy
+// of each view's volume (the reference's vm_IB), then band by band the weights of both images and
+// the aggregation of every view's rows of that band.  Lab planes and raw copies are the group's own
+// pairs' slices and each stream has its own band, so groups on different streams share no scratch.
+sm_status run_aws(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w) {
+    const sm_params& p = c->p;
+    const size_t off = (size_t)(B.vm0 - c->vm0) / c->nvol, cap = c->cap, nv = c->nvol, np = c->npix;
+    int slot = 0;
+    for (int i = 0; i < 3; i++)
+        if (c->xst[i] && c->st == c->xst[i]) slot = i + 1;
+    if (!c->aws_band[slot]) return fail(c, SM_ESTATE, "aggregation AWS: no weight band for this stream");
+    sm::AwsArgs a{};
+    a.tab = c->aws_tab;
+    a.bgr = B.bgr;
+    a.lab = c->aws_lab + off * 2 * np * 3;
+    a.wt = c->aws_band[slot];
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.rv = c->aws_rv;
+    a.ru = c->aws_ru;
+    a.gamma_c = c->aws_gamma;
+    a.band_rows = c->aws_band_rows;
+    a.solve_all = solve_all;
+    a.scale = w;
+    const int views = n_views(p);
+    const double S = (double)(2 * a.rv + 1) * (2 * a.ru + 1);
+    sm_status s = timed(c, "aws_lab", (double)n * 2 * np * 6, [&] { sm::launch_aws_lab(a, n, c->st); });
+    if (s) return s;
+    for (int v = 0; v < views; v++) {
+        float* vm = v == 0 ? B.vm0 : B.vm1;
+        float* raw = c->aws_raw + ((size_t)v * cap + off) * nv;
+        if ((s = timed(c, v == 0 ? "aws_copy" : "aws_copy_r", (double)n * nv * 8, [&] {
+                 hipMemcpyAsync(raw, vm, (size_t)n * nv * 4, hipMemcpyDeviceToDevice, c->st);
+             })))
+            return s;
+    }
+    const int rows = n * p.rows;
+    for (int r0 = 0; r0 < rows; r0 += c->aws_band_rows) {
+        a.r0 = r0;
+        a.nr = std::min(c->aws_band_rows, rows - r0);
+        if ((s = timed(c, "aws_weights", (double)a.nr * p.cols * S * 8, [&] { sm::launch_aws_weights(a, c->st); }))) return s;
+        for (int v = 0; v < views; v++) {
+            a.raw = c->aws_raw + ((size_t)v * cap + off) * nv;
+            a.out = v == 0 ? B.vm0 : B.vm1;
+            a.lor = v;
+            if ((s = timed(c, v == 0 ? "aws_agg" : "aws_agg_r", (double)a.nr * p.cols * p.num_disparities * 8,
+                           [&] { sm::launch_aws_agg(a, c->st); })))
+                return s;
+        }
+    }
+    return SM_OK;
+}
+
+// aggregation other than CBCA: GF, FIF and AWS on every view (num = Do_refine ? 2 : 1, cpp:4499, 4709-4711),
 // NL on vm[0]
 sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false, float w = 1.f) {
     sm_status s = SM_OK;
@@ -857,6 +965,7 @@ sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false,
         for (int v = 0; v < n_views(c->p) && !s; v++) s = run_gf(c, n, v, B, solve_all, w);
     if (c->p.aggregation == SM_AGG_FIF)
         for (int v = 0; v < n_views(c->p) && !s; v++) s = run_fif(c, n, v, B, solve_all, w);
+    if (c->p.aggregation == SM_AGG_AWS) s = run_aws(c, n, B, solve_all, w);
     if (c->p.aggregation == SM_AGG_NL) s = run_nl(c, n, B, solve_all, w);
     return s;
 }
@@ -1242,6 +1351,20 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         if ((s = dalloc(c, &c->fif_s, (c->acc ? 1 : 2) * cap * c->nvol))) return s;
         if ((s = dalloc(c, &c->fif_w, 2 * cap * c->npix))) return s;
     }
+    if (p->aggregation == SM_AGG_AWS) {
+        if ((s = dalloc(c, &c->aws_tab, (size_t)sm::AWS_GAM_N + sm::AWS_CB_N))) return s;
+        HIP_TRY(c, hipMemcpy(c->aws_tab, aws_tables(), (sm::AWS_GAM_N + sm::AWS_CB_N) * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if ((s = dalloc(c, &c->aws_lab, cap * 2 * c->npix * 3))) return s;
+        if ((s = dalloc(c, &c->aws_raw, (size_t)n_views(*p) * cap * c->nvol))) return s;
+        // the bands are sized for radius 17 (sm_aws_config may set any smaller window later)
+        const size_t smax = (size_t)(2 * sm::AWS_MAX_R + 1) * (2 * sm::AWS_MAX_R + 1);
+        const size_t row_bytes = 2 * smax * p->cols * 4;
+        // SM_AWS_BAND_BYTES: a smaller budget (tests: images of a few rows then span several bands)
+        size_t budget = AWS_BAND_BYTES;
+        if (const char* e = getenv("SM_AWS_BAND_BYTES")) budget = std::min<size_t>(budget, strtoull(e, nullptr, 10));
+        const size_t fit = std::max<size_t>(1, budget / row_bytes);
+        c->aws_band_rows = (int)std::min<size_t>({fit, cap * (size_t)p->rows, (size_t)32767});   // (2 x rows is a grid dimension)
+    }
     if (p->aggregation == SM_AGG_NL) {
         const size_t ne = (size_t)p->rows * (p->cols - 1) + (size_t)(p->rows - 1) * p->cols;
         if ((s = dalloc(c, &c->nl_med, cap * c->npix * 3))) return s;
@@ -1294,6 +1417,7 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         // rule; cost_scan_fused decides per view whether the configuration is eligible
         c->fuse_cost_scan = p->fuse_cost_scan != 0;
         if ((s = apply_schedule(c, p->num_streams, p->sub_batch))) return s;
+        if ((s = aws_alloc_bands(c))) return s;
         for (int i = 0; i < 16; i++) {
             hipEvent_t e;
             HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1703,8 +1827,8 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
             if (c->p.aggregation == SM_AGG_CBCA && c->p.cbca_iterations > 0)
                 s_out = run_cbca(c, m2, v, true, w, B);   // SolveAll fused into the last pass
             else if (!SM_FUSE_SOLVE_ALL || !(c->p.aggregation == SM_AGG_GF || c->p.aggregation == SM_AGG_FIF ||
-                                             (c->p.aggregation == SM_AGG_NL && v == 0)))
-                s_out = run_scale(c, m2, v, w, B);      // (GF, FIF and NL's vm[0]: fused above)
+                                             c->p.aggregation == SM_AGG_AWS || (c->p.aggregation == SM_AGG_NL && v == 0)))
+                s_out = run_scale(c, m2, v, w, B);      // (GF, FIF, AWS and NL's vm[0]: fused above)
         }
         if (s_out) break;
         // the maps are written from here on: an asynchronous copy of the previous run's maps
@@ -2006,6 +2130,7 @@ sm_status sm_set_schedule(sm_ctx* c, int32_t num_streams, int32_t sub_batch) {
     // (the previous sm_run joined its side streams into the main stream, so the next run's
     // groups are ordered after it whichever streams they use)
     if ((s = apply_schedule(c, num_streams, sub_batch))) return s;
+    if ((s = aws_alloc_bands(c))) return s;
     c->p.num_streams = num_streams;
     c->p.sub_batch = sub_batch;
     return SM_OK;
@@ -2106,6 +2231,38 @@ sm_status sm_cal_err(const int16_t* DP, const float* DT, const uint8_t* mask, in
 }
 
 float sm_expf_host(float x) { return sm::expf_host(x); }
+
+sm_status sm_aws_config(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gamma_c) {
+    // host state only (launches already queued carry their constants by value): no device call,
+    // so the arguments are checked on a machine without a GPU too
+    if (!c) return SM_EINVAL;
+    if (c->p.aggregation != SM_AGG_AWS) return fail(c, SM_EINVAL, "sm_aws_config: the context's aggregation is not SM_AGG_AWS");
+    if (radius_v < 0 || radius_v > sm::AWS_MAX_R) return fail(c, SM_EINVAL, "radius_v must be in [0, 17]");
+    if (radius_u < 0 || radius_u > sm::AWS_MAX_R) return fail(c, SM_EINVAL, "radius_u must be in [0, 17]");
+    if (!(gamma_c > 0) || !std::isfinite(gamma_c)) return fail(c, SM_EINVAL, "gamma_c must be finite and > 0");
+    c->aws_rv = radius_v;
+    c->aws_ru = radius_u;
+    c->aws_gamma = gamma_c;
+    return SM_OK;
+}
+
+void sm_bgr2lab_host(const uint8_t* bgr, size_t npix, uint8_t* lab) {
+    if (!bgr || !lab) return;
+    const uint16_t* tab = aws_tables();
+    for (size_t i = 0; i < npix; i++) sm::aws_lab_px(tab, bgr[3 * i], bgr[3 * i + 1], bgr[3 * i + 2], lab + 3 * i);
+}
+
+sm_status sm_get_aws_lab(sm_ctx* c, int32_t view, uint8_t* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst) return fail(c, SM_EINVAL, "null dst");
+    if (c->p.aggregation != SM_AGG_AWS) return fail(c, SM_EINVAL, "sm_get_aws_lab: the context's aggregation is not SM_AGG_AWS");
+    if (view != 0 && view != 1) return fail(c, SM_EINVAL, "bad view");
+    if (c->stage < 2) return fail(c, SM_ESTATE, "no Lab plane yet");
+    HIP_TRY(c, hipMemcpyAsync(dst, c->aws_lab + (size_t)view * c->npix * 3, c->npix * 3, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
 
 sm_status sm_expf_device_range(sm_ctx* c, uint32_t first_bits, uint32_t n, float* out) {
     sm_status s = check(c);

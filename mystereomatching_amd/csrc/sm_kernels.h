@@ -153,6 +153,45 @@ struct FifArgs {                // full-image guided filter "FIF" (sm_fif.hip); 
 void launch_fif_weights(const FifArgs& a, int n, hipStream_t st);
 void launch_fif_sweep(const FifArgs& a, int n, hipStream_t st);
 
+// Adaptive support weights "AWS" (sm_aws.hip).
+constexpr int AWS_MAX_R = 17;                       // W_V_AWS = W_U_AWS = 17 (cpp:5715), the largest radius
+constexpr int AWS_GAM_N = 256, AWS_CB_N = 3072;     // the 8-bit BGR2Lab tables: [gam | cb], uint16 each
+
+// One pixel of OpenCV's 8-bit BGR2Lab (fixed point; PARITY UNPINNED).  tab = gam[256] | cb[3072].
+__host__ __device__ inline void aws_lab_px(const uint16_t* tab, int B, int G, int R, uint8_t* lab) {
+    const uint16_t* cb = tab + AWS_GAM_N;
+    const int b = tab[B], g = tab[G], r = tab[R];
+    const int fx = cb[(r * 1777 + g * 1541 + b * 778 + 2048) >> 12];
+    const int fy = cb[(r * 871 + g * 2929 + b * 296 + 2048) >> 12];
+    const int fz = cb[(r * 73 + g * 448 + b * 3575 + 2048) >> 12];
+    const int L = (296 * fy - 1336934 + 16384) >> 15;
+    const int A = (500 * (fx - fy) + 128 * 32768 + 16384) >> 15;
+    const int Bb = (200 * (fy - fz) + 128 * 32768 + 16384) >> 15;
+    lab[0] = (uint8_t)(L < 0 ? 0 : L > 255 ? 255 : L);
+    lab[1] = (uint8_t)(A < 0 ? 0 : A > 255 ? 255 : A);
+    lab[2] = (uint8_t)(Bb < 0 ? 0 : Bb > 255 ? 255 : Bb);
+}
+
+struct AwsArgs {                // pair-relative bases; a "row unit" r is row r % H of pair r / H
+    const uint16_t* tab;        // gam | cb
+    const uint8_t* bgr;         // [n][2][H][W][3]
+    uint8_t* lab;               // [n][2][H][W][3] (L, a, b) of both images
+    float* wt;                  // the weight band: [2 images][band rows][S][W], row units r0 .. r0 + nr
+    const float* raw;           // [n][H][W][D] the view's raw costs (the reference's vm_IB, unbordered)
+    float* out;                 // [n][H][W][D] the view's volume (raw on entry: elements out of range stay)
+    int H, W, D;
+    int rv, ru;                 // window radii, each in [0, AWS_MAX_R]
+    float gamma_c;
+    int r0, nr;                 // the band's first row unit and its row count
+    int band_rows;              // rows the band buffer holds per image (the image stride is band_rows * S * W)
+    int lor;                    // the view (calvm_AWS<LOR>)
+    int solve_all;              // 1: the store is SolveAll's `0 + w * q` (cpp:2189-2201), raw elements included
+    float scale;
+};
+void launch_aws_lab(const AwsArgs& a, int n, hipStream_t st);
+void launch_aws_weights(const AwsArgs& a, hipStream_t st);
+void launch_aws_agg(const AwsArgs& a, hipStream_t st);
+
 struct NlArgs {                 // non-local tree filter (sm_nl.hip); node ids = pair * H W + pixel
     const int4* rec;            // path nodes, each path bottom -> top: {x, meta, child weights, parent}
                                 //   meta = nchild | (heavy + 1) << 3 | child directions << 6 (2 bits

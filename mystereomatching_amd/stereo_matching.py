@@ -42,6 +42,9 @@ class StereoMatching:
     # costCalculate's "FIF" branch calls FIF_Improve (cpp:1010-1012, `//FIF();` commented out):
     # True selects the plain form FIF (cpp:4541-4705) instead
     FIF_PLAIN = False
+    # AWS()'s function-local constants (W_V_AWS, W_U_AWS cpp:5715; r_c h:1478), read with
+    # aggregation = "AWS" (sm_aws_config)
+    AWS_RADIUS_V, AWS_RADIUS_U, AWS_GAMMA_C = _capi.AWS_DEFAULTS
     Do_regionVote = True
     Do_properIpol = True
     Do_lastMedianBlur = True
@@ -150,6 +153,9 @@ class StereoMatching:
         st = self._lib.sm_create(C.byref(ctx), C.byref(p), device)
         self._ctx = ctx
         _capi.check(self._lib, ctx, st, "sm_create")
+        if self.aggregation == "AWS":
+            st = self._lib.sm_aws_config(ctx, int(self.AWS_RADIUS_V), int(self.AWS_RADIUS_U), float(self.AWS_GAMMA_C))
+            _capi.check(self._lib, ctx, st, "sm_aws_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -276,6 +282,8 @@ class StereoBatch:
     def __init__(self, max_disp: int, rows: int, cols: int, batch: int, device: int = 0, **overrides):
         self._lib = _capi.load()
         overrides.setdefault("batch_capacity", batch)
+        # "AWS"'s constants are not sm_params fields (sm_aws_config): aws_radius_v / _u, aws_gamma_c
+        aws = [overrides.pop(k, d) for k, d in zip(("aws_radius_v", "aws_radius_u", "aws_gamma_c"), _capi.AWS_DEFAULTS)]
         p = _capi.default_params(max_disp, rows, cols, **overrides)
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
@@ -283,6 +291,8 @@ class StereoBatch:
         st = self._lib.sm_create(C.byref(ctx), C.byref(p), device)
         self._ctx = ctx
         _capi.check(self._lib, ctx, st, "sm_create")
+        if tuple(aws) != _capi.AWS_DEFAULTS:
+            self.aws_config(*aws)
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -392,6 +402,11 @@ class StereoBatch:
         st = self._lib.sm_copy_ceiling(self._ctx, int(nbytes), int(reps), C.byref(best), C.byref(med))
         _capi.check(self._lib, self._ctx, st, "copy_ceiling")
         return best.value, med.value
+
+    def aws_config(self, radius_v: int = 17, radius_u: int = 17, gamma_c: float = 5.0):
+        """sm_aws_config: "AWS"'s window radii (each in [0, 17]) and gamma_c, from the next run on."""
+        st = self._lib.sm_aws_config(self._ctx, int(radius_v), int(radius_u), float(gamma_c))
+        _capi.check(self._lib, self._ctx, st, "aws_config")
 
     def set_schedule(self, num_streams: int = 0, sub_batch: int = 0):
         """sm_set_schedule: num_streams / sub_batch for the following runs on the same allocations

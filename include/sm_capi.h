@@ -14,7 +14,11 @@
  *                         (aggregators: cbca cpp:5585-5666, guideFilter cpp:4492-4516, NL cpp:4892-4917,
  *                          FIF_Improve cpp:4707-4890 and its plain form FIF cpp:4541-4705,
  *                          AWS cpp:5692-5801 without JBF_STANDARD, h:1305-1350, 1472-1493, 1533-1548)
+ *                          BF cpp:1023-1043, GFNL cpp:4421-4490)
  *   sm_aws_config      <- AWS()'s local constants W_V_AWS, W_U_AWS (cpp:5715) and r_c (h:1478)
+ *   sm_bf_config       <- BF()'s literal Size(12, 12) (cpp:1038)
+ *   sm_gfnl_config     <- GFNL()'s literal variance threshold 400 (cpp:4470)
+ *   sm_get_gfnl_mask   <- member arm_Mask as GFNL() leaves it (cpp:4460, 4472)
  *   sm_solve_all       <- SolveAll(StereoMatching**&, PY_LVL, REG_LAMBDA)  stereoMatching.cpp:2142-2208
  *   sm_solve_all_pyr   <- the same with PY_LVL > 1 (one ctx per level)     stereoMatching.cpp:2142-2208
  *   sm_pyr_down        <- cv::pyrDown on the inputs                     main_.cpp:145-148
@@ -73,6 +77,14 @@ typedef enum sm_aggregation {
     SM_AGG_AWS = 7,          /* "AWS" adaptive support weights over a 35 x 35 window (cpp:5692-5801, the branch
                               * without JBF_STANDARD); window and gamma_c: sm_aws_config.  The Lab planes are
                               * OpenCV's 8-bit BGR2Lab restated (parity unpinned) */
+    /* 8 is reserved (rejected by sm_create).  The gaps 4, 6 and 8 are deliberate and pinned by tests: do not
+     * renumber or fill them */
+    SM_AGG_BF = 9,           /* "BF" cv::boxFilter(vm[i], vm[i], -1, Size(12, 12)) on every view that exists
+                              * (cpp:1023-1043): normalised, BORDER_REFLECT_101, anchor 6, i.e. offsets -6 .. +5;
+                              * window: sm_bf_config.  Costs stay >= +0: every optimiser applies */
+    SM_AGG_GFNL = 10,        /* "GFNL" (cpp:4421-4490): vm[0] = NL where the left gray image's 19 x 19 variance is
+                              * < 400 (sm_gfnl_config), else (float)(0.5 NL + 0.5 GF); vm[1] is GF's (do_refine).
+                              * Reads gf_eps, gf_mode, nl_sigma; like GF, sgm / WTA only */
 } sm_aggregation;
 
 /* "FIF"'s two forms: */
@@ -293,7 +305,22 @@ SM_API sm_status sm_cal_err(const int16_t* disp, const float* gt, const uint8_t*
  * argument named in sm_last_error, on a bad value or a context whose aggregation is not SM_AGG_AWS. */
 SM_API sm_status sm_aws_config(sm_ctx* ctx, int32_t radius_v, int32_t radius_u, float gamma_c);
 
+/* "BF"'s window, a literal in the reference (Size(12, 12), cpp:1038; width = ksize_u, height = ksize_v): each
+ * size in [1, 32], anchor ksize / 2 (an even window reaches one further up / left than down / right).  Defaults
+ * 12, 12.  Applies from the next sm_cost_calculate / sm_run.  SM_EINVAL, with the argument named in
+ * sm_last_error, on a size out of range, on an image too small for a single reflection
+ * (rows < ksize_v / 2 + 1 or cols < ksize_u / 2 + 1), or on a context whose aggregation is not SM_AGG_BF. */
+SM_API sm_status sm_bf_config(sm_ctx* ctx, int32_t ksize_v, int32_t ksize_u);
+
+/* "GFNL"'s variance threshold, a literal in the reference (400, cpp:4470): any finite float.  The 19 x 19
+ * window and the 0.5 / 0.5 blend are fixed.  Applies from the next sm_cost_calculate / sm_run.  SM_EINVAL on
+ * a value that is not finite or on a context whose aggregation is not SM_AGG_GFNL. */
+SM_API sm_status sm_gfnl_config(sm_ctx* ctx, float var_thresh);
+
 /* Diagnostics used by the parity tests. */
+/* "GFNL": pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where the variance
+ * is below the threshold, i.e. where vm[0] is NL's value alone). */
+SM_API sm_status sm_get_gfnl_mask(sm_ctx* ctx, uint8_t* dst);
 /* "AWS": OpenCV's 8-bit BGR2Lab on the host (no device needed) with the tables the kernels use:
  * npix packed BGR pixels -> npix packed (L, a, b); and the H x W x 3 plane the device computed for
  * pair 0's image `view` in the last sm_cost_calculate / sm_run. */

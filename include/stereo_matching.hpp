@@ -344,6 +344,10 @@ class StereoMatching {
     // aggregation == "AWS" (sm_aws_config: radii in [0, 17], gamma_c > 0)
     inline static int aws_radius_v = 17, aws_radius_u = 17;
     inline static float aws_gamma_c = 5.0f;
+    // BF()'s literal Size(12, 12) (cpp:1038; height, width) and GFNL()'s literal variance threshold
+    // (cpp:4470), read with aggregation == "BF" / "GFNL" (sm_bf_config, sm_gfnl_config)
+    inline static int bf_ksize_v = 12, bf_ksize_u = 12;
+    inline static float gfnl_var_thresh = 400.0f;
 
     struct Parameters {  // StereoMatching::Parameters (h:85-351), the fields the hot path reads
         int numDisparities, rows, cols;
@@ -495,7 +499,7 @@ class StereoMatching {
                                                         : -1;
         if (p.cost_method < 0) throw std::invalid_argument("unsupported costcalculation: " + costcalculation);
         if (aggregation != "CBCA" && aggregation != "GF" && aggregation != "NL" && aggregation != "FIF" &&
-            aggregation != "AWS" && !aggregation.empty())
+            aggregation != "AWS" && aggregation != "BF" && aggregation != "GFNL" && !aggregation.empty())
             throw std::invalid_argument("unsupported aggregation: " + aggregation);
         if (optimization != "sgm" && optimization != "so" && !optimization.empty())
             throw std::invalid_argument("unsupported optimization: " + optimization);
@@ -504,6 +508,8 @@ class StereoMatching {
                         : aggregation == "NL" ? SM_AGG_NL
                         : aggregation == "FIF" ? SM_AGG_FIF
                         : aggregation == "AWS" ? SM_AGG_AWS
+                        : aggregation == "BF" ? SM_AGG_BF
+                        : aggregation == "GFNL" ? SM_AGG_GFNL
                                               : SM_AGG_NONE;
         p.optimization = optimization == "sgm" ? SM_OPT_SGM : (optimization == "so" ? SM_OPT_SO : SM_OPT_WTA);
         p.census_ring = param.censusFunc == 3;
@@ -532,6 +538,8 @@ class StereoMatching {
         p.lr_consis = Do_LRConsis ? 1 : 0;
         check(sm_create(&ctx_, &p, hip_device), "sm_create");
         if (aggregation == "AWS") check(sm_aws_config(ctx_, aws_radius_v, aws_radius_u, aws_gamma_c), "sm_aws_config");
+        if (aggregation == "BF") check(sm_bf_config(ctx_, bf_ksize_v, bf_ksize_u), "sm_bf_config");
+        if (aggregation == "GFNL") check(sm_gfnl_config(ctx_, gfnl_var_thresh), "sm_gfnl_config");
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }
     void check(sm_status s, const char* what) {

@@ -13,9 +13,12 @@ LIB_PATH = os.path.join(_HERE, "libsm_hip.so")
 
 SM_OK, SM_EINVAL, SM_ENOMEM, SM_EHIP, SM_ESTATE = 0, 1, 2, 3, 4
 COST_METHODS = {"censusGrad": 0, "Census": 1, "ADCensus": 2, "AD": 3}
-AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3, "FIF": 5, "AWS": 7}   # 4 and 6 are reserved
+AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3, "FIF": 5, "AWS": 7,
+                "BF": 9, "GFNL": 10}   # 4, 6 and 8 are reserved
 FIF_IMPROVE, FIF_PLAIN = 0, 1
 AWS_DEFAULTS = (17, 17, 5.0)   # radius_v, radius_u, gamma_c (sm_aws_config)
+BF_DEFAULTS = (12, 12)         # ksize_v, ksize_u (sm_bf_config)
+GFNL_VAR_THRESH = 400.0        # sm_gfnl_config
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -97,6 +100,9 @@ SIGNATURES = [
     ("sm_aws_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_float]),
     ("sm_bgr2lab_host", None, [_P, C.c_size_t, _P]),
     ("sm_get_aws_lab", C.c_int, [_P, C.c_int32, _P]),
+    ("sm_bf_config", C.c_int, [_P, C.c_int32, C.c_int32]),
+    ("sm_gfnl_config", C.c_int, [_P, C.c_float]),
+    ("sm_get_gfnl_mask", C.c_int, [_P, _P]),
 ]
 
 _lib = None

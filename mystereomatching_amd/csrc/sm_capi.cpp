@@ -90,7 +90,14 @@ struct sm_ctx {
     float* aws_raw = nullptr;      // [views][cap][nvol]
     float* aws_band[4] = {nullptr, nullptr, nullptr, nullptr};   // each [2][aws_band_rows][S][W]
     int aws_band_rows = 0;
-    // aggregation "NL": median image, edge weights, spanning trees, the tree walk, filter values
+    // aggregation "BF": the window (sm_bf_config) and the row sums between the two sweeps
+    int bf_kv = 12, bf_ku = 12;
+    double* bf_rs = nullptr;       // [cap][nvol]
+    // aggregation "GFNL": the variance threshold (sm_gfnl_config), the NL result, arm_Mask
+    float gfnl_thresh = 400.0f;
+    float* gfnl_res = nullptr;     // [cap][nvol]
+    uint8_t* gfnl_mask = nullptr;  // [cap][npix]
+    // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
     int* nl_ints = nullptr;     // two sets of: chain_start, chain_len, order_up, order_down [cap][npix] each
@@ -246,6 +253,23 @@ int n_views(const sm_params& p) { return p.do_refine ? 2 : 1; }   // imgNum = Do
 // SolveAll touch vm[1] only with Do_refine, cpp:5592, 2178)
 int opt_views(const sm_params& p) { return p.optimization == SM_OPT_SO ? (p.lr_consis ? 2 : 1) : n_views(p); }
 
+// "GFNL" runs GF's and NL's code with their parameters and buffers
+bool uses_gf(const sm_params& p) { return p.aggregation == SM_AGG_GF || p.aggregation == SM_AGG_GFNL; }
+bool uses_nl(const sm_params& p) { return p.aggregation == SM_AGG_NL || p.aggregation == SM_AGG_GFNL; }
+
+// "BF" keeps every cost >= +0 (as the SGM / WTA / so minima on bit patterns assume) because its
+// sums are exact: every cost is 0 or a multiple of 2^-25 below 2^10, so a double holds
+// any sum of <= 1024 of them.  Census costs are integers <= 136; AD costs are fl(s / 3), s <= 765
+// an integer (0 or in [1/3, 255]: multiples of 2^-25), or ad_trunc_ad itself, which must then be
+// such a multiple too; censusGrad and ADCensus costs are fl(t - e) with t = fl(2 - e0) in [1, 2] a
+// multiple of 2^-23 and e in [0, 1]: a result >= 1/2 has ulp >= 2^-24, a smaller one has e > 1/2,
+// a multiple of 2^-24, and is exact.
+bool bf_exact(const sm_params& p) {
+    if (p.cost_method != SM_COST_AD) return true;
+    const float t = p.ad_trunc_ad;
+    return t <= 1024.0f && std::ldexp(t, 25) == std::floor(std::ldexp(t, 25));
+}
+
 int cbca_lag(const sm_params& p) { return p.arm_l_out > p.arm_min_l ? p.arm_l_out : p.arm_min_l; }
 
 // Every dividend of iteration k's normalisation (genfinalVm_cbca, cpp:3969-3992) is 0 or
@@ -281,8 +305,27 @@ sm_status validate(const sm_params& p, std::string& why) {
     if (p.rows > 65535) return bad("rows must be <= 65535");
     if (p.num_disparities < 1 || p.num_disparities > 1024) return bad("num_disparities must be in [1, 1024]");
     if (p.cost_method < 0 || p.cost_method > 3) return bad("unknown cost_method");
-    if (p.aggregation < 0 || p.aggregation > SM_AGG_AWS || p.aggregation == 4 || p.aggregation == 6)
-        return bad("unknown aggregation");   // (4, 6: reserved)
+    if (p.aggregation < 0 || p.aggregation > SM_AGG_GFNL || p.aggregation == 4 || p.aggregation == 6 || p.aggregation == 8)
+        return bad("unknown aggregation");   // (4, 6, 8: reserved)
+    if (p.aggregation == SM_AGG_BF) {
+        // the default 12 x 12 window (anchor 6) with one REFLECT_101 reflection
+        if (p.rows < 7 || p.cols < 7) return bad("aggregation BF needs rows, cols >= 7 (12 x 12 box, reflected border)");
+        if (p.optimization == SM_OPT_SO && !bf_exact(p))
+            return bad("aggregation BF with optimization so needs ad_trunc_ad a multiple of 2^-25 and <= 1024 (exact sums)");
+    }
+    if (p.aggregation == SM_AGG_GFNL) {
+        if (p.gf_mode != SM_GF_XIMGPROC && p.gf_mode != SM_GF_MY_GUIDE)
+            return bad("aggregation GFNL: gf_mode must be 0 (ximgproc::guidedFilter) or 1 (MY_GUIDE)");
+        if (p.gf_mode == SM_GF_MY_GUIDE && (p.rows < 19 || p.cols < 19))
+            return bad("aggregation GFNL (MY_GUIDE) needs rows, cols >= 19 (box radius 9)");
+        // the variance plane's 19 x 19 box with REFLECT_101 (one reflection); covers GF's >= 9 and NL's >= 3
+        if (p.rows < 10 || p.cols < 10) return bad("aggregation GFNL needs rows, cols >= 10 (19 x 19 variance box, reflected border)");
+        if (p.optimization == SM_OPT_SO) return bad("aggregation GFNL (costs may be negative) supports optimization sgm or WTA");
+        if (!(p.gf_eps > 0)) return bad("aggregation GFNL: gf_eps must be > 0");
+        if (!(p.nl_sigma > 0)) return bad("aggregation GFNL: nl_sigma must be > 0");
+        if (4.0 * (double)p.rows * (double)p.cols * (double)(p.batch_capacity > 0 ? p.batch_capacity : 1) >= 2147483647.0)
+            return bad("aggregation GFNL: rows * cols * batch_capacity must stay below 2^29");
+    }
     if (p.aggregation == SM_AGG_AWS) {   // the kernels' 32-bit offsets inside a volume row and a weight row
         if (p.cols > (1 << 21) || (long long)p.cols * p.num_disparities >= (1LL << 29))
             return bad("aggregation AWS needs cols <= 2^21 and cols * num_disparities < 2^29");
@@ -407,7 +450,8 @@ void free_all(sm_ctx* c) {
                     c->gf_s, c->gf_planes, c->gf_pix, c->gfc_rs, c->gfc_ab, c->gfc_img, c->gfc_pix, c->nl_med, c->nl_ew, c->nl_ints, c->nl_rec,
                     c->nl_table, c->nl_val, c->nl_oup, c->nl_ofin, c->nl_par, c->nl_best, c->nl_mst, c->nl_adj, c->nl_walk,
                     c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w,
-                    c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3]};
+                    c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3],
+                    c->bf_rs, c->gfnl_res, c->gfnl_mask};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -534,7 +578,7 @@ sm_status run_prep(sm_ctx* c, int n, const Bufs& B) {
         a.do_arms = arms;
         a.do_flags = flags;
         // the packed BGR plane's later readers: the GF image planes, so, refine's properIpol
-        a.pack_px = p.aggregation == SM_AGG_GF || p.optimization == SM_OPT_SO || p.do_refine;
+        a.pack_px = uses_gf(p) || p.optimization == SM_OPT_SO || p.do_refine;
         return timed(c, "prep", (double)n * 2 * c->npix * (1 + 3 + (census ? 16 : 0) + (arms ? 8 : 0)) +
                                     (flags ? (double)n * c->npix * n_views(p) : 0),
                      [&] { sm::launch_prep(a, n, c->st); });
@@ -715,7 +759,8 @@ sm_status run_gf(sm_ctx* c, int n, int view, const Bufs& B, bool solve_all, floa
 #define SM_NL_PIPE 1   // sm_run: NL's prep and cost volume on the front stream (A/B switch)
 #endif
 // all on the GPU (sm_nl.hip, sm_nl_mst.hip, sm_nl_walk.hip)
-sm_status run_nl(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w, Bufs* pipe = nullptr) {
+// `out`: where the filtered volume goes instead of vm[0] ("GFNL" keeps the raw costs for GF)
+sm_status run_nl(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w, Bufs* pipe = nullptr, float* out = nullptr) {
     const size_t off = (size_t)(B.vm0 - c->vm0) / c->nvol, np = c->npix;
     const int H = c->p.rows, W = c->p.cols, D = c->p.num_disparities;
     const size_t ne = (size_t)H * (W - 1) + (size_t)(H - 1) * W;
@@ -790,7 +835,7 @@ sm_status run_nl(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w, Bufs*
     a.rec = (const int4*)rec_d;
     a.table = c->nl_table;
     a.val = c->nl_val;
-    a.vm = B.vm0;
+    a.vm = out ? out : B.vm0;
     a.vc = pipe ? pipe->vm0 : B.vm0;
     a.oup = c->nl_oup;
     a.ofin = c->nl_ofin;
@@ -957,8 +1002,59 @@ sm_status run_aws(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w) {
     return SM_OK;
 }
 
+// BF() (cpp:1023-1043; sm_bf.hip) on one view: the row sweep into the double row sums, the column
+// sweep back into the volume.  The row sums are the group's own pairs' slice, shared by its views
+// (they run one after the other on the group's stream).
+sm_status run_bf(sm_ctx* c, int n, int view, const Bufs& B, bool solve_all, float w) {
+    const sm_params& p = c->p;
+    const size_t off = (size_t)(B.vm0 - c->vm0) / c->nvol, nv = c->nvol;
+    sm::BfArgs a{};
+    a.vm = view == 0 ? B.vm0 : B.vm1;
+    a.rs = c->bf_rs + off * nv;
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.kv = c->bf_kv;
+    a.ku = c->bf_ku;
+    a.solve_all = solve_all;
+    a.scale = w;
+    if (p.rows < a.kv / 2 + 1 || p.cols < a.ku / 2 + 1) return fail(c, SM_ESTATE, "aggregation BF: the window does not fit the image");
+    sm_status s = timed(c, view == 0 ? "bf_rows" : "bf_rows_r", (double)n * nv * 12, [&] { sm::launch_bf_rows(a, n, c->st); });
+    if (s) return s;
+    return timed(c, view == 0 ? "bf_cols" : "bf_cols_r", (double)n * nv * 12, [&] { sm::launch_bf_cols(a, n, c->st); });
+}
+
+// GFNL() (cpp:4421-4490): NL of the raw vm[0] into its own volume, guideFilter in place on every
+// view (num = Do_refine ? 2 : 1, cpp:4499), then on vm[0] the blend under the left gray image's
+// variance mask (sm_bf.hip).  SolveAll's scale goes into the blend's store (vm[0]) and into GF's
+// last store (vm[1]).  All scratch is the group's own pairs' slices.
+sm_status run_gfnl(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w) {
+    const sm_params& p = c->p;
+    const size_t off = (size_t)(B.vm0 - c->vm0) / c->nvol, nv = c->nvol, np = c->npix;
+    float* res = c->gfnl_res + off * nv;
+    sm_status s = run_nl(c, n, B, false, 1.f, nullptr, res);
+    if (s) return s;
+    if ((s = run_gf(c, n, 0, B, false, 1.f))) return s;
+    if (n_views(p) == 2 && (s = run_gf(c, n, 1, B, solve_all, w))) return s;
+    sm::GfnlArgs a{};
+    a.gray = B.gray;   // I_g[0]
+    a.gray_pair_stride = 2 * np;
+    a.mask = c->gfnl_mask + off * np;
+    a.res = res;
+    a.vm = B.vm0;
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.thresh = c->gfnl_thresh;
+    a.solve_all = solve_all;
+    a.scale = w;
+    if ((s = timed(c, "gfnl_mask", (double)n * np * 2, [&] { sm::launch_gfnl_mask(a, n, c->st); }))) return s;
+    return timed(c, "gfnl_blend", (double)n * nv * 12 + (double)n * np, [&] { sm::launch_gfnl_blend(a, n, c->st); });
+}
+
 // aggregation other than CBCA: GF, FIF and AWS on every view (num = Do_refine ? 2 : 1, cpp:4499, 4709-4711),
-// NL on vm[0]
+// NL on vm[0], BF on every view that exists (imgNum = Do_LRConsis ? 2 : 1, cpp:1025); SolveAll touches
+// vm[1] only with Do_refine (cpp:2178)
 sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false, float w = 1.f) {
     sm_status s = SM_OK;
     if (c->p.aggregation == SM_AGG_GF)
@@ -967,6 +1063,9 @@ sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false,
         for (int v = 0; v < n_views(c->p) && !s; v++) s = run_fif(c, n, v, B, solve_all, w);
     if (c->p.aggregation == SM_AGG_AWS) s = run_aws(c, n, B, solve_all, w);
     if (c->p.aggregation == SM_AGG_NL) s = run_nl(c, n, B, solve_all, w);
+    if (c->p.aggregation == SM_AGG_BF)
+        for (int v = 0; v < (right_view(c->p) ? 2 : 1) && !s; v++) s = run_bf(c, n, v, B, solve_all && v < n_views(c->p), w);
+    if (c->p.aggregation == SM_AGG_GFNL) s = run_gfnl(c, n, B, solve_all, w);
     return s;
 }
 
@@ -998,7 +1097,8 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
         // the guided filter's output can be < 0.  FIF's cannot (so it stays false there, and "so"
         // applies too): with costs and weights >= +0 rounding is monotone, so c1, c2 >= vm, hence
         // fl(c1 + c2) >= vm and A = fl(fl(c1 + c2) - vm) >= +0; the vertical pass likewise
-        a.signed_costs = p.aggregation == SM_AGG_GF;
+        // BF's are >= +0 while its sums are exact (bf_exact)
+        a.signed_costs = uses_gf(p) || (p.aggregation == SM_AGG_BF && !bf_exact(p));
         int first = 0;   // first path left to the plain sweeps
         if (B.ck) {
             // checkpointed pairs (0, 1) and (2, 3): 4 + 8 + 4 + 8 B per element (+ 4 / S for
@@ -1337,12 +1437,12 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         if ((s = dalloc(c, &c->disp_tmp, cap * c->npix))) return s;
     }
     if ((s = dalloc(c, &c->px, 3 * cap * 2 * c->npix))) return s;
-    if (p->aggregation == SM_AGG_GF && p->gf_mode == SM_GF_XIMGPROC) {
+    if (uses_gf(*p) && p->gf_mode == SM_GF_XIMGPROC) {
         if ((s = dalloc(c, &c->gfc_rs, 4 * cap * c->nvol))) return s;
         if ((s = dalloc(c, &c->gfc_ab, 4 * cap * c->nvol))) return s;
         if ((s = dalloc(c, &c->gfc_img, cap * 9 * c->npix))) return s;
         if ((s = dalloc(c, &c->gfc_pix, cap * 9 * c->npix))) return s;
-    } else if (p->aggregation == SM_AGG_GF) {
+    } else if (uses_gf(*p)) {
         if ((s = dalloc(c, &c->gf_s, (c->acc ? 3 : 4) * cap * c->nvol))) return s;
         if ((s = dalloc(c, &c->gf_planes, cap * 10 * c->npix))) return s;
         if ((s = dalloc(c, &c->gf_pix, cap * c->npix))) return s;
@@ -1365,7 +1465,13 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         const size_t fit = std::max<size_t>(1, budget / row_bytes);
         c->aws_band_rows = (int)std::min<size_t>({fit, cap * (size_t)p->rows, (size_t)32767});   // (2 x rows is a grid dimension)
     }
-    if (p->aggregation == SM_AGG_NL) {
+    if (p->aggregation == SM_AGG_BF)
+        if ((s = dalloc(c, &c->bf_rs, cap * c->nvol))) return s;
+    if (p->aggregation == SM_AGG_GFNL) {
+        if ((s = dalloc(c, &c->gfnl_res, cap * c->nvol))) return s;
+        if ((s = dalloc(c, &c->gfnl_mask, cap * c->npix))) return s;
+    }
+    if (uses_nl(*p)) {
         const size_t ne = (size_t)p->rows * (p->cols - 1) + (size_t)(p->rows - 1) * p->cols;
         if ((s = dalloc(c, &c->nl_med, cap * c->npix * 3))) return s;
         if ((s = dalloc(c, &c->nl_ew, cap * ne))) return s;
@@ -1384,7 +1490,7 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         if ((s = dalloc(c, &c->nl_mst, sm::nl_mst_scratch_bytes(p->rows, p->cols, cap)))) return s;
         if ((s = dalloc(c, &c->nl_adj, cap * c->npix))) return s;
         // sm_run's pipelined front (one view, SGM): two sets of cost volume and penalty flags
-        c->nl_pipe = SM_NL_PIPE && p->optimization == SM_OPT_SGM && !right_view(*p);
+        c->nl_pipe = SM_NL_PIPE && p->aggregation == SM_AGG_NL && p->optimization == SM_OPT_SGM && !right_view(*p);
         if (c->nl_pipe) {
             if ((s = dalloc(c, &c->nl_vc, 2 * cap * c->nvol + vpad))) return s;
             if ((s = dalloc(c, &c->nl_fl, 2 * cap * c->npix))) return s;
@@ -1827,8 +1933,9 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
             if (c->p.aggregation == SM_AGG_CBCA && c->p.cbca_iterations > 0)
                 s_out = run_cbca(c, m2, v, true, w, B);   // SolveAll fused into the last pass
             else if (!SM_FUSE_SOLVE_ALL || !(c->p.aggregation == SM_AGG_GF || c->p.aggregation == SM_AGG_FIF ||
-                                             c->p.aggregation == SM_AGG_AWS || (c->p.aggregation == SM_AGG_NL && v == 0)))
-                s_out = run_scale(c, m2, v, w, B);      // (GF, FIF, AWS and NL's vm[0]: fused above)
+                                             c->p.aggregation == SM_AGG_AWS || c->p.aggregation == SM_AGG_BF ||
+                                             c->p.aggregation == SM_AGG_GFNL || (c->p.aggregation == SM_AGG_NL && v == 0)))
+                s_out = run_scale(c, m2, v, w, B);      // (GF, FIF, AWS, BF, GFNL and NL's vm[0]: fused above)
         }
         if (s_out) break;
         // the maps are written from here on: an asynchronous copy of the previous run's maps
@@ -2243,6 +2350,38 @@ sm_status sm_aws_config(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gam
     c->aws_rv = radius_v;
     c->aws_ru = radius_u;
     c->aws_gamma = gamma_c;
+    return SM_OK;
+}
+
+sm_status sm_bf_config(sm_ctx* c, int32_t ksize_v, int32_t ksize_u) {
+    // host state only, like sm_aws_config
+    if (!c) return SM_EINVAL;
+    if (c->p.aggregation != SM_AGG_BF) return fail(c, SM_EINVAL, "sm_bf_config: the context's aggregation is not SM_AGG_BF");
+    if (ksize_v < 1 || ksize_v > sm::BF_MAX_K) return fail(c, SM_EINVAL, "ksize_v must be in [1, 32]");
+    if (ksize_u < 1 || ksize_u > sm::BF_MAX_K) return fail(c, SM_EINVAL, "ksize_u must be in [1, 32]");
+    if (c->p.rows < ksize_v / 2 + 1) return fail(c, SM_EINVAL, "ksize_v: rows must be >= ksize_v / 2 + 1 (one reflection)");
+    if (c->p.cols < ksize_u / 2 + 1) return fail(c, SM_EINVAL, "ksize_u: cols must be >= ksize_u / 2 + 1 (one reflection)");
+    c->bf_kv = ksize_v;
+    c->bf_ku = ksize_u;
+    return SM_OK;
+}
+
+sm_status sm_gfnl_config(sm_ctx* c, float var_thresh) {
+    if (!c) return SM_EINVAL;
+    if (c->p.aggregation != SM_AGG_GFNL) return fail(c, SM_EINVAL, "sm_gfnl_config: the context's aggregation is not SM_AGG_GFNL");
+    if (!std::isfinite(var_thresh)) return fail(c, SM_EINVAL, "var_thresh must be finite");
+    c->gfnl_thresh = var_thresh;
+    return SM_OK;
+}
+
+sm_status sm_get_gfnl_mask(sm_ctx* c, uint8_t* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst) return fail(c, SM_EINVAL, "null dst");
+    if (c->p.aggregation != SM_AGG_GFNL) return fail(c, SM_EINVAL, "sm_get_gfnl_mask: the context's aggregation is not SM_AGG_GFNL");
+    if (c->stage < 2) return fail(c, SM_ESTATE, "no mask yet");
+    HIP_TRY(c, hipMemcpyAsync(dst, c->gfnl_mask, c->npix, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
     return SM_OK;
 }
 

@@ -131,6 +131,34 @@ struct GfCvArgs {               // guided filter, ximgproc form (sm_gf_cv.hip); 
 };
 void launch_gf_cv(const GfCvArgs& a, int n, hipStream_t st);
 
+// cv::boxFilter (normalised, BORDER_REFLECT_101, anchor k / 2) on a volume: aggregation "BF" (sm_bf.hip)
+constexpr int BF_MAX_K = 32;    // the largest window side sm_bf_config accepts
+struct BfArgs {                 // pair-relative bases
+    float* vm;                  // [n][H][W][D], filtered in place (rows read it, cols write it)
+    double* rs;                 // [n][H][W][D] row sums
+    int H, W, D;
+    int kv, ku;                 // window height and width, each in [1, BF_MAX_K]; H >= kv / 2 + 1, W >= ku / 2 + 1
+    int solve_all;              // 1: the output is SolveAll's `0 + w * q` (cpp:2189-2201), w = scale
+    float scale;
+};
+void launch_bf_rows(const BfArgs& a, int n, hipStream_t st);
+void launch_bf_cols(const BfArgs& a, int n, hipStream_t st);
+
+// aggregation "GFNL"'s variance mask and blend (sm_bf.hip); pair-relative bases
+struct GfnlArgs {
+    const uint8_t* gray;        // pair b's left gray image at gray + b * gray_pair_stride; H, W >= 10
+    size_t gray_pair_stride;
+    uint8_t* mask;              // [n][H][W] arm_Mask: 1 where the 19 x 19 variance is < thresh
+    const float* res;           // [n][H][W][D] the NL result
+    float* vm;                  // [n][H][W][D] the GF result on entry, the blend on return
+    int H, W, D;
+    float thresh;
+    int solve_all;              // 1: the store is SolveAll's `0 + w * q`, w = scale
+    float scale;
+};
+void launch_gfnl_mask(const GfnlArgs& a, int n, hipStream_t st);
+void launch_gfnl_blend(const GfnlArgs& a, int n, hipStream_t st);
+
 struct FifArgs {                // full-image guided filter "FIF" (sm_fif.hip); pair-relative bases
     // k_fif_weights: the view's colour image -> the weight planes
     const uint8_t* bgr;         // the view's colour image of pair 0

@@ -45,6 +45,10 @@ class StereoMatching:
     # AWS()'s function-local constants (W_V_AWS, W_U_AWS cpp:5715; r_c h:1478), read with
     # aggregation = "AWS" (sm_aws_config)
     AWS_RADIUS_V, AWS_RADIUS_U, AWS_GAMMA_C = _capi.AWS_DEFAULTS
+    # BF()'s literal Size(12, 12) (cpp:1038; height, width) and GFNL()'s literal variance threshold
+    # (cpp:4470), read with aggregation = "BF" / "GFNL" (sm_bf_config, sm_gfnl_config)
+    BF_KSIZE_V, BF_KSIZE_U = _capi.BF_DEFAULTS
+    GFNL_VAR_THRESH = _capi.GFNL_VAR_THRESH
     Do_regionVote = True
     Do_properIpol = True
     Do_lastMedianBlur = True
@@ -156,6 +160,12 @@ class StereoMatching:
         if self.aggregation == "AWS":
             st = self._lib.sm_aws_config(ctx, int(self.AWS_RADIUS_V), int(self.AWS_RADIUS_U), float(self.AWS_GAMMA_C))
             _capi.check(self._lib, ctx, st, "sm_aws_config")
+        if self.aggregation == "BF":
+            st = self._lib.sm_bf_config(ctx, int(self.BF_KSIZE_V), int(self.BF_KSIZE_U))
+            _capi.check(self._lib, ctx, st, "sm_bf_config")
+        if self.aggregation == "GFNL":
+            st = self._lib.sm_gfnl_config(ctx, float(self.GFNL_VAR_THRESH))
+            _capi.check(self._lib, ctx, st, "sm_gfnl_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -284,6 +294,9 @@ class StereoBatch:
         overrides.setdefault("batch_capacity", batch)
         # "AWS"'s constants are not sm_params fields (sm_aws_config): aws_radius_v / _u, aws_gamma_c
         aws = [overrides.pop(k, d) for k, d in zip(("aws_radius_v", "aws_radius_u", "aws_gamma_c"), _capi.AWS_DEFAULTS)]
+        # likewise "BF"'s window (sm_bf_config) and "GFNL"'s threshold (sm_gfnl_config)
+        bf = [overrides.pop(k, d) for k, d in zip(("bf_ksize_v", "bf_ksize_u"), _capi.BF_DEFAULTS)]
+        gfnl_thresh = overrides.pop("gfnl_var_thresh", _capi.GFNL_VAR_THRESH)
         p = _capi.default_params(max_disp, rows, cols, **overrides)
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
@@ -293,6 +306,10 @@ class StereoBatch:
         _capi.check(self._lib, ctx, st, "sm_create")
         if tuple(aws) != _capi.AWS_DEFAULTS:
             self.aws_config(*aws)
+        if tuple(bf) != _capi.BF_DEFAULTS:
+            self.bf_config(*bf)
+        if gfnl_thresh != _capi.GFNL_VAR_THRESH:
+            self.gfnl_config(gfnl_thresh)
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -407,6 +424,16 @@ class StereoBatch:
         """sm_aws_config: "AWS"'s window radii (each in [0, 17]) and gamma_c, from the next run on."""
         st = self._lib.sm_aws_config(self._ctx, int(radius_v), int(radius_u), float(gamma_c))
         _capi.check(self._lib, self._ctx, st, "aws_config")
+
+    def bf_config(self, ksize_v: int = 12, ksize_u: int = 12):
+        """sm_bf_config: "BF"'s window height and width (each in [1, 32]), from the next run on."""
+        st = self._lib.sm_bf_config(self._ctx, int(ksize_v), int(ksize_u))
+        _capi.check(self._lib, self._ctx, st, "bf_config")
+
+    def gfnl_config(self, var_thresh: float = 400.0):
+        """sm_gfnl_config: "GFNL"'s variance threshold (any finite value), from the next run on."""
+        st = self._lib.sm_gfnl_config(self._ctx, float(var_thresh))
+        _capi.check(self._lib, self._ctx, st, "gfnl_config")
 
     def set_schedule(self, num_streams: int = 0, sub_batch: int = 0):
         """sm_set_schedule: num_streams / sub_batch for the following runs on the same allocations

@@ -63,6 +63,31 @@ typedef enum sm_cost_method {
     SM_COST_CENSUS = 1,      /* "Census"     (cpp:975-976) */
     SM_COST_AD_CENSUS = 2,   /* "ADCensus"   (cpp:894-915, 5250-5277) */
     SM_COST_AD = 3,          /* "AD"         (cpp:954-955) */
+    /* The remaining measures of costCalculate (cpp:954-987).  Left view, moving pixel u - d (the right view
+     * mirrors it); fl = one fp32 rounding; constants that are literals in the reference's functions are fixed. */
+    SM_COST_SD = 4,          /* "SD"  asdCal(vm, "SD", imgNum, 20) (cpp:954-955) -> gen_ad_sd_vm(.., AOS = 1, trunc)
+                              * (cpp:2468-2509): min(fl(sum_c |L_c - R_c|^2 / 3), ad_trunc_ad), out of range
+                              * ad_trunc_ad (the call and its argument are AD's) */
+    SM_COST_BT = 5,          /* "BT"  bt (cpp:90-114): Birchfield-Tomasi on the gray images (calNeiMaxMin cpp:197-227,
+                              * calCostForBT cpp:142-195): the smaller distance of one pixel's value to the other
+                              * pixel's half-neighbour range; truncation and out-of-range value 20 */
+    SM_COST_GRAD = 6,        /* "grad"  grad(vm, 500) (cpp:961-962, 603-656) -> calgradvm: the gradient term of
+                              * censusGrad stored as is; reads grad_trunc and grad_adaptive; out of range
+                              * (float)sqrt(2 grad_trunc^2) */
+    /* 7 is reserved (rejected by sm_create): "ZNCC".  gen_NCC_vm (cpp:2419-2464) writes only the interior of an
+     * uninitialised volume that transform_NCCVm2 (cpp:2692-2707) then reads whole, so the reference's output
+     * is undefined on a border frame and there is nothing to match.  The gap is pinned by tests */
+    SM_COST_TRUNC_AD = 8,    /* "TruncAD"  truncAD (cpp:788-805) -> gen_truncAD_vm (cpp:2511-2548):
+                              * (float)min(sum_c |L_c - R_c|, 60) in integers, out of range 60 */
+    SM_COST_AD_GRAD = 9,     /* "adGrad"  adGrad (cpp:50-70): A = AD with truncation 7, G = grad with truncation 2,
+                              * fl(fl(A * (float)0.11) + fl(G * (float)(1 - 0.11))) (gen_vm_from2vm_fixWgt
+                              * cpp:3767-3796); reads grad_adaptive */
+    SM_COST_AD_CENSUS_GRAD = 10, /* "ADCensusGrad"  ADCensusGrad (cpp:917-943) -> gen_vm_from3vm_exp (cpp:3592-3652,
+                              * called from cpp:5287): A = AD with truncation 255, C = the census cost, G = grad with
+                              * truncation 500; m = (float)(0.5 A + 0.5 C), (float)(0.7 (1 - expf(-m / 1)) +
+                              * 0.3 (1 - expf(-G / 2))) with the products and the sum in double.  The call's ARU
+                              * arguments 30, 45, 15 are dead in the live line (cpp:3640); reads grad_adaptive and
+                              * the census window */
 } sm_cost_method;
 
 typedef enum sm_aggregation {

@@ -496,6 +496,12 @@ class StereoMatching {
                         : costcalculation == "Census"   ? SM_COST_CENSUS
                         : costcalculation == "ADCensus" ? SM_COST_AD_CENSUS
                         : costcalculation == "AD"       ? SM_COST_AD
+                        : costcalculation == "SD"       ? SM_COST_SD
+                        : costcalculation == "BT"       ? SM_COST_BT
+                        : costcalculation == "grad"     ? SM_COST_GRAD
+                        : costcalculation == "TruncAD"  ? SM_COST_TRUNC_AD
+                        : costcalculation == "adGrad"   ? SM_COST_AD_GRAD
+                        : costcalculation == "ADCensusGrad" ? SM_COST_AD_CENSUS_GRAD
                                                         : -1;
         if (p.cost_method < 0) throw std::invalid_argument("unsupported costcalculation: " + costcalculation);
         if (aggregation != "CBCA" && aggregation != "GF" && aggregation != "NL" && aggregation != "FIF" &&

@@ -12,7 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsm_hip.so")
 
 SM_OK, SM_EINVAL, SM_ENOMEM, SM_EHIP, SM_ESTATE = 0, 1, 2, 3, 4
-COST_METHODS = {"censusGrad": 0, "Census": 1, "ADCensus": 2, "AD": 3}
+# costCalculate's strings (cpp:954-987) with sm_cost_method's values; "ZNCC" (7, reserved) is left out on
+# purpose: the reference's ZNCC volume is undefined on a border frame
+COST_METHODS = {"censusGrad": 0, "Census": 1, "ADCensus": 2, "AD": 3, "SD": 4, "BT": 5, "grad": 6, "TruncAD": 8,
+                "adGrad": 9, "ADCensusGrad": 10}
 AGGREGATIONS = {"": 0, "none": 0, "CBCA": 1, "GF": 2, "NL": 3, "FIF": 5, "AWS": 7,
                 "BF": 9, "GFNL": 10}   # 4, 6 and 8 are reserved
 FIF_IMPROVE, FIF_PLAIN = 0, 1

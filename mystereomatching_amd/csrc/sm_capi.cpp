@@ -238,9 +238,23 @@ sm_status timed(sm_ctx* c, const char* name, double bytes, F&& launch) {
 
 int census_len(const sm_params& p) { return (2 * p.census_rv + 1) * (2 * p.census_ru + 1) + (p.census_ring ? 8 : 0); }
 
-bool needs_census(const sm_params& p) { return p.cost_method != SM_COST_AD; }
+// the measures of sm_cost_ext.hip (SD .. ADCensusGrad) and, among them, those with a gradient term
+bool cost_ext(const sm_params& p) { return p.cost_method >= SM_COST_SD; }
+bool cost_has_grad_ext(const sm_params& p) {
+    return p.cost_method == SM_COST_GRAD || p.cost_method == SM_COST_AD_GRAD || p.cost_method == SM_COST_AD_CENSUS_GRAD;
+}
+const char* cost_name(int m) {
+    static const char* const names[] = {"censusGrad", "Census", "ADCensus", "AD", "SD", "BT", "grad", "?", "TruncAD", "adGrad",
+                                        "ADCensusGrad"};
+    return m >= 0 && m <= SM_COST_AD_CENSUS_GRAD ? names[m] : "?";
+}
+bool needs_census(const sm_params& p) {
+    return cost_ext(p) ? p.cost_method == SM_COST_AD_CENSUS_GRAD : p.cost_method != SM_COST_AD;
+}
 bool needs_arms(const sm_params& p) {
-    return p.cost_method == SM_COST_CENSUS_GRAD || p.aggregation == SM_AGG_CBCA || p.do_refine;  // + regionVote (cpp:1393-1396)
+    // grad() builds the arms for its adaptive weights (cpp:630-633)
+    return p.cost_method == SM_COST_CENSUS_GRAD || cost_has_grad_ext(p) || p.aggregation == SM_AGG_CBCA ||
+           p.do_refine;  // + regionVote (cpp:1393-1396)
 }
 // "so" runs on both views when Do_LRConsis (num = Do_LRConsis ? 2 : 1, cpp:1093, Do_LRConsis = 1,
 // h:72; imgNum = Do_LRConsis ? 2 : 1 in costCalculate, cpp:952), so DP[1] = so(vm[1]) needs the
@@ -263,9 +277,13 @@ bool uses_nl(const sm_params& p) { return p.aggregation == SM_AGG_NL || p.aggreg
 // an integer (0 or in [1/3, 255]: multiples of 2^-25), or ad_trunc_ad itself, which must then be
 // such a multiple too; censusGrad and ADCensus costs are fl(t - e) with t = fl(2 - e0) in [1, 2] a
 // multiple of 2^-23 and e in [0, 1]: a result >= 1/2 has ulp >= 2^-24, a smaller one has e > 1/2,
-// a multiple of 2^-24, and is exact.
+// a multiple of 2^-24, and is exact.  SD costs are fl(s / 3), s <= 195075 (0 or in [1/3, 2^16): multiples of
+// 2^-25; their sums of <= 1024 stay below 2^26, 51 bits above 2^-25) or ad_trunc_ad, under AD's rule; BT costs
+// are multiples of 1/2 <= 20, TruncAD costs integers <= 60.  The measures with a gradient term (grad, adGrad,
+// ADCensusGrad) have no such proof.
 bool bf_exact(const sm_params& p) {
-    if (p.cost_method != SM_COST_AD) return true;
+    if (cost_has_grad_ext(p)) return false;
+    if (p.cost_method != SM_COST_AD && p.cost_method != SM_COST_SD) return true;
     const float t = p.ad_trunc_ad;
     return t <= 1024.0f && std::ldexp(t, 25) == std::floor(std::ldexp(t, 25));
 }
@@ -290,6 +308,13 @@ bool cbca_div_safe(const sm_params& p, int k) {
         if (p.ad_trunc_ad == 0.0f) return true;   // every cost is 0
         const float m = std::min(1.0f / 3.0f, p.ad_trunc_ad);
         f0 = std::ilogb(m);
+    } else if (p.cost_method == SM_COST_SD) {   // SD: min(s / 3, trunc), s an integer
+        if (p.ad_trunc_ad == 0.0f) return true;
+        f0 = std::ilogb(std::min(1.0f / 3.0f, p.ad_trunc_ad));
+    } else if (p.cost_method == SM_COST_BT) {   // multiples of 1/2
+        f0 = -1;
+    } else if (p.cost_method == SM_COST_TRUNC_AD) {   // integers
+        f0 = 0;
     } else {
         return false;   // a cost method without a proof keeps the IEEE fallback
     }
@@ -304,12 +329,18 @@ sm_status validate(const sm_params& p, std::string& why) {
     if ((long long)p.rows * p.cols > (1LL << 30)) return bad("rows*cols too large");
     if (p.rows > 65535) return bad("rows must be <= 65535");
     if (p.num_disparities < 1 || p.num_disparities > 1024) return bad("num_disparities must be in [1, 1024]");
-    if (p.cost_method < 0 || p.cost_method > 3) return bad("unknown cost_method");
+    // (7 is reserved: "ZNCC", whose reference output is undefined on a border frame)
+    if (p.cost_method < 0 || p.cost_method > SM_COST_AD_CENSUS_GRAD || p.cost_method == 7) return bad("unknown cost_method");
     if (p.aggregation < 0 || p.aggregation > SM_AGG_GFNL || p.aggregation == 4 || p.aggregation == 6 || p.aggregation == 8)
         return bad("unknown aggregation");   // (4, 6, 8: reserved)
     if (p.aggregation == SM_AGG_BF) {
         // the default 12 x 12 window (anchor 6) with one REFLECT_101 reflection
         if (p.rows < 7 || p.cols < 7) return bad("aggregation BF needs rows, cols >= 7 (12 x 12 box, reflected border)");
+        if (p.optimization == SM_OPT_SO && cost_has_grad_ext(p)) {
+            const std::string msg = std::string("aggregation BF with optimization so is not supported for cost_method ") + cost_name(p.cost_method) +
+                  " (its box sums are not exact, so a filtered cost may be -0)";
+            return bad(msg.c_str());
+        }
         if (p.optimization == SM_OPT_SO && !bf_exact(p))
             return bad("aggregation BF with optimization so needs ad_trunc_ad a multiple of 2^-25 and <= 1024 (exact sums)");
     }
@@ -620,6 +651,21 @@ sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
     a.ad_trunc = p.ad_trunc_ad;
     a.ad_oor_exp = c->ad_oor_exp;
     a.lut = c->luts;
+    if (cost_ext(p)) {
+        // the literals of the reference's call sites: adGrad gen_ad_sd_vm(.., 0, 7), grad(.., 2) (cpp:60-62);
+        // ADCensusGrad asdCal("AD", .., 255), grad(.., 500) (cpp:930-935); SD shares asdCal(.., 20) with AD
+        if (p.cost_method == SM_COST_AD_GRAD) {
+            a.ad_trunc = 7.0f;
+            a.grad_trunc = 2.0f;
+        } else if (p.cost_method == SM_COST_AD_CENSUS_GRAD) {
+            a.ad_trunc = 255.0f;
+            a.grad_trunc = 500.0f;
+        }
+        a.grad_oor = (float)sqrt(pow((double)a.grad_trunc, 2) * 2);
+        const int m = p.cost_method;   // sm::SM_M_SD .. carry sm_cost_method's values
+        return timed(c, view == 0 ? "cost_volume" : "cost_volume_right", (double)n * c->nvol * 4.0,
+                     [&] { sm::launch_cost_ext(a, m, n, c->st); });
+    }
     const int m = p.cost_method == SM_COST_CENSUS_GRAD ? sm::SM_M_CENSUS_GRAD
                   : p.cost_method == SM_COST_CENSUS    ? sm::SM_M_CENSUS
                   : p.cost_method == SM_COST_AD_CENSUS ? sm::SM_M_AD_CENSUS

@@ -7,6 +7,8 @@
 namespace sm {
 
 enum { SM_M_CENSUS_GRAD = 0, SM_M_CENSUS = 1, SM_M_AD_CENSUS = 2, SM_M_AD = 3 };
+// the measures of k_cost_ext (sm_cost_ext.hip, launch_cost_ext); the values are sm_cost_method's (7 is reserved)
+enum { SM_M_SD = 4, SM_M_BT = 5, SM_M_GRAD = 6, SM_M_TRUNC_AD = 8, SM_M_AD_GRAD = 9, SM_M_AD_CENSUS_GRAD = 10 };
 enum { SGM_FIRST = 1, SGM_LAST = 2, SGM_KEEP = 4, SGM_SIGNED = 8 };  // KEEP: last path also writes the summed volume;
 // SIGNED: costs may be negative (the guided filter's output), minima compare as floats
 enum { CB_SCAN = 0, CB_NORM = 1, CB_NORM_SCAN = 2 };
@@ -275,6 +277,10 @@ struct PyrArgs {                // SolveAll over PY_LVL pyramid levels (sm_pyram
 };
 
 void launch_cost(const CostArgs& a, int method, int n, hipStream_t st);
+// methods SM_M_SD .. SM_M_AD_CENSUS_GRAD (sm_cost_ext.hip).  CostArgs as launch_cost reads them, with
+// ad_trunc the measure's AD / SD truncation (SD: ad_trunc_ad; adGrad 7; ADCensusGrad 255) and
+// grad_trunc / grad_oor its gradient truncation (grad: grad_trunc; adGrad 2; ADCensusGrad 500)
+void launch_cost_ext(const CostArgs& a, int method, int n, hipStream_t st);
 void launch_prep(const PrepArgs& a, int n, hipStream_t st);
 size_t prep_smem_bytes(int rv, int ru, int L_out);
 void launch_cbca(const CbcaArgs& a, bool horiz, int mode, int n, hipStream_t st);

@@ -26,7 +26,10 @@
  *   sm_disp_optimize   <- StereoMatching::dispOptimize + DP[0]       stereoMatching.cpp:1046-1136, h:2724
  *   sm_refine          <- StereoMatching::refine (Do_refine)         stereoMatching.cpp:1138-1511, main_.cpp:165-166
  *   sm_get_disp / sm_set_disp <- public member DP[view]              stereoMatching.h:2724
- *   sm_get_volume      <- public member vm[view]                     stereoMatching.h:2720
+ *   sm_vmtop_config    <- Parameters::Do_vmTop, vmTop_* and ts       stereoMatching.h:182-188, 201, 320-326
+ *                         (dispOptimize cpp:1108-1128, selectTopCostFromVolumn h:2405-2461,
+ *                          genDispFromTopCostVm2 cpp:1514-1885)
+ *   sm_get_volume / sm_set_volume <- public member vm[view]       stereoMatching.h:2720
  *   sm_get_arms        <- public member HVL[view]                    stereoMatching.h:2717
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
  *   sm_run / sm_run_batch  <- the whole main_.cpp:139-163 sequence for n independent pairs
@@ -341,6 +344,29 @@ SM_API sm_status sm_bf_config(sm_ctx* ctx, int32_t ksize_v, int32_t ksize_u);
  * window and the 0.5 / 0.5 blend are fixed.  Applies from the next sm_cost_calculate / sm_run.  SM_EINVAL on
  * a value that is not finite or on a context whose aggregation is not SM_AGG_GFNL. */
 SM_API sm_status sm_gfnl_config(sm_ctx* ctx, float var_thresh);
+
+/* dispOptimize's Do_vmTop branch (cpp:1108-1128), the candidate-disparity selection: after "sgm" or "" every pixel
+ * keeps the `num` (vmTop_Num = M, main:62) cheapest disparities whose cost is < firstV * thres (vmTop_thres =
+ * (float)(lamc * 0.01), h:323; selectTopCostFromVolumn, h:2405-2461) and genDispFromTopCostVm2 (cpp:1514-1885)
+ * chooses among them with vmTop_method 0 (the default: pairs of candidates closer than ts, a cost-keyed
+ * container, the 8 neighbours' candidates; vmTop_hasCir2, vmTop_cir3_doColorLimit), 1 or 2 (row-sequential).
+ * Not sm_params fields (the struct keeps its size): off by default, takes effect from the next sm_disp_optimize /
+ * sm_run.  With it on, SGM writes its path sum into vm[view] (as with keep_final_volume) and the selection reads
+ * it; "" reads the volume after SolveAll; with do_refine both views are done and refine() runs on those maps;
+ * "so" never reaches the branch, so the call is accepted there and changes nothing.  The maps are the same for
+ * every schedule.  The candidate table is allocated on the first enabling call (batch_capacity pairs, every
+ * view dispOptimize runs on).  SM_EINVAL, with the argument named in sm_last_error, for a method outside
+ * [0, 2], a num outside [1, 8] or a thres that is not finite; the arguments are checked without a device.
+ * Costs are expected finite and below FLT_MAX (the reference masks taken disparities with FLT_MAX). */
+SM_API sm_status sm_vmtop_config(sm_ctx* ctx, int32_t enable, int32_t method, int32_t num, float thres, int32_t ts,
+                                 int32_t has_cir2, int32_t cir3_color_limit);
+/* Overwrite vm[view] of pair 0 (the reference's vm is a public member, h:2717), H*W*D floats; after
+ * sm_cost_calculate.  sm_disp_optimize may then run (again) on it. */
+SM_API sm_status sm_set_volume(sm_ctx* ctx, int32_t view, const float* src);
+/* Pair 0's candidate table of `view` from the last sm_disp_optimize / sm_run with vmTop on, in the reference's
+ * topDisp layout [H][W][num + 1][2] floats: (disparity, cost) per kept candidate, the count in [num][0];
+ * entries the reference never writes read as 0. */
+SM_API sm_status sm_get_top_disp(sm_ctx* ctx, int32_t view, float* dst);
 
 /* Diagnostics used by the parity tests. */
 /* "GFNL": pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where the variance

@@ -354,6 +354,13 @@ class StereoMatching {
         int lamCen, lamG, disSc;
         int vmTop_Num, ts;
         float vmTop_thres;
+        // dispOptimize's candidate-disparity selection (h:182-188, 320-326; sm_vmtop_config): set before the
+        // object is constructed
+        bool Do_vmTop = false;
+        int vmTop_method = 0;
+        int vmTop_thres_dirNum = 8;           // carried; genDispFromTopCostVm2 does not read it
+        bool vmTop_hasCir2 = true;
+        bool vmTop_cir3_doColorLimit = false;
         std::string errCsvName;
         int censusFunc = 3;                   // h:244
         int cbca_iterationNum = 2, cbca_minArmL = 1;
@@ -367,7 +374,8 @@ class StereoMatching {
         Parameters(int maxDisp, int h, int w, int lamCen_ = 13, int lamG_ = 1, int M = 2, int lamc = 109,
                    int ts_ = 10, const std::string& errCsvName_ = "", int disSc_ = 1)
             : numDisparities(maxDisp + 1), rows(h), cols(w), lamCen(lamCen_), lamG(lamG_), disSc(disSc_),
-              vmTop_Num(M), ts(ts_), vmTop_thres(lamc * 0.01f), errCsvName(errCsvName_) {}
+              vmTop_Num(M), ts(ts_), vmTop_thres((float)(lamc * 0.01)),   // the product in double, then one rounding (h:323)
+              errCsvName(errCsvName_) {}
     };
 
     struct RegionErr {            // one line of calErr's report (h:1798-1799)
@@ -546,6 +554,10 @@ class StereoMatching {
         if (aggregation == "AWS") check(sm_aws_config(ctx_, aws_radius_v, aws_radius_u, aws_gamma_c), "sm_aws_config");
         if (aggregation == "BF") check(sm_bf_config(ctx_, bf_ksize_v, bf_ksize_u), "sm_bf_config");
         if (aggregation == "GFNL") check(sm_gfnl_config(ctx_, gfnl_var_thresh), "sm_gfnl_config");
+        if (param.Do_vmTop)
+            check(sm_vmtop_config(ctx_, 1, param.vmTop_method, param.vmTop_Num, param.vmTop_thres, param.ts,
+                                  param.vmTop_hasCir2 ? 1 : 0, param.vmTop_cir3_doColorLimit ? 1 : 0),
+                  "sm_vmtop_config");
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }
     void check(sm_status s, const char* what) {

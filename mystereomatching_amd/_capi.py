@@ -106,6 +106,9 @@ SIGNATURES = [
     ("sm_bf_config", C.c_int, [_P, C.c_int32, C.c_int32]),
     ("sm_gfnl_config", C.c_int, [_P, C.c_float]),
     ("sm_get_gfnl_mask", C.c_int, [_P, _P]),
+    ("sm_vmtop_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32]),
+    ("sm_set_volume", C.c_int, [_P, C.c_int32, _P]),
+    ("sm_get_top_disp", C.c_int, [_P, C.c_int32, _P]),
 ]
 
 _lib = None

@@ -97,6 +97,16 @@ struct sm_ctx {
     float gfnl_thresh = 400.0f;
     float* gfnl_res = nullptr;     // [cap][nvol]
     uint8_t* gfnl_mask = nullptr;  // [cap][npix]
+    // dispOptimize's Do_vmTop branch (sm_vmtop_config): the settings, the candidate tables and counts of every
+    // view dispOptimize runs on, and method 0's pending-pixel counts per anti-diagonal
+    bool vt_on = false;
+    int vt_method = 0, vt_num = 2, vt_ts = 10, vt_cir2 = 1, vt_color = 0;
+    float vt_thres = 1.09f;
+    float2* vt_tab = nullptr;      // [views][cap][npix][vt_num] (disparity, cost)
+    int* vt_cnt = nullptr;         // [views][cap][npix]
+    int* vt_tcnt = nullptr;        // [cap][cols + 2 rows]
+    int vt_alloc_num = 0;          // candidates per pixel the table is sized for
+    int vt_ran_num[2] = {0, 0};    // vt_num of the last selection on each view (0: none), for sm_get_top_disp
     // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -482,7 +492,7 @@ void free_all(sm_ctx* c) {
                     c->nl_table, c->nl_val, c->nl_oup, c->nl_ofin, c->nl_par, c->nl_best, c->nl_mst, c->nl_adj, c->nl_walk,
                     c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w,
                     c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3],
-                    c->bf_rs, c->gfnl_res, c->gfnl_mask};
+                    c->bf_rs, c->gfnl_res, c->gfnl_mask, c->vt_tab, c->vt_cnt, c->vt_tcnt};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -1115,11 +1125,58 @@ sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false,
     return s;
 }
 
+// Do_vmTop (cpp:1111-1121): selectTopCostFromVolumn on vm[view] as the optimiser left it, then
+// genDispFromTopCostVm2 into DP[view]; I_c[0] is the colour image for both views
+sm_status run_vmtop(sm_ctx* c, int n, int view, const Bufs& B, const float* vm, int16_t* disp) {
+    const sm_params& p = c->p;
+    const size_t off = (size_t)(B.disp - c->disp) / c->npix;   // the group's first pair
+    const size_t T = (size_t)p.cols + 2 * (size_t)p.rows;
+    const char* sfx = view == 0 ? "" : "_r";
+    sm::VmTopArgs a{};
+    a.vm = vm;
+    a.tab = c->vt_tab + ((size_t)view * c->cap + off) * c->npix * c->vt_num;
+    a.cnt = c->vt_cnt + ((size_t)view * c->cap + off) * c->npix;
+    a.tcnt = c->vt_tcnt + off * T;
+    a.bgr = B.bgr;
+    a.disp = disp;
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.M = c->vt_num;
+    a.n = n;
+    a.thres = c->vt_thres;
+    a.method = c->vt_method;
+    a.ts = c->vt_ts;
+    a.has_cir2 = c->vt_cir2;
+    a.color_limit = c->vt_color;
+    const double np = (double)n * c->npix, tab = 8.0 * a.M + 4;
+    sm_status s = timed(c, (std::string("vmtop_select") + sfx).c_str(), (double)n * c->nvol * 4.0 + np * tab,
+                        [&] { sm::launch_vmtop_select(a, c->st); });
+    if (s) return s;
+    c->vt_ran_num[view] = a.M;
+    if (a.method == 0) {
+        HIP_TRY(c, hipMemsetAsync(a.tcnt, 0, (size_t)n * T * sizeof(int), c->st));
+        if ((s = timed(c, (std::string("vmtop_decide0_a") + sfx).c_str(), np * (9 * tab + 2),
+                       [&] { sm::launch_vmtop_decide0_a(a, c->st); })))
+            return s;
+        for (int r = 0; r < sm::VMTOP_RELAX_ROUNDS; r++)
+            if ((s = timed(c, (std::string("vmtop_decide0_w") + sfx).c_str(), np * 2, [&] { sm::launch_vmtop_decide0_w(a, c->st); })))
+                return s;
+        return timed(c, (std::string("vmtop_decide0_b") + sfx).c_str(), (double)n * T * 4 + np * 2,
+                     [&] { sm::launch_vmtop_decide0_b(a, c->st); });
+    }
+    return timed(c, (std::string("vmtop_decide12") + sfx).c_str(), np * (tab + 2), [&] { sm::launch_vmtop_decide12(a, c->st); });
+}
+
 sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
     const sm_params& p = c->p;
     float* vm = view == 0 ? B.vm0 : B.vm1;
     int16_t* disp = view == 0 ? B.disp : B.disp1;
     const char* sfx = view == 0 ? "" : "_r";
+    // Do_vmTop replaces gen_dispFromVm after "sgm" and "" (cpp:1108-1128); "so" never reaches it.  SGM then
+    // writes its path sum into vm[view] (the keep_final_volume path) for the selection to read
+    const bool vmtop = c->vt_on && p.optimization != SM_OPT_SO;
+    const int keep_final = p.keep_final_volume || vmtop;
     if (p.optimization == SM_OPT_SGM) {
         static const int RV[8] = {+1, -1, 0, 0, +1, +1, -1, -1};  // cpp:6207
         static const int RU[8] = {0, 0, +1, -1, -1, +1, +1, -1};  // cpp:6208
@@ -1139,7 +1196,7 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
         a.p2 = p.sgm_p2;
         a.cor_thres = p.sgm_cor_dif_thres;
         a.redu = p.sgm_redu_coeff;
-        a.keep_final = p.keep_final_volume;
+        a.keep_final = keep_final;
         // the guided filter's output can be < 0.  FIF's cannot (so it stays false there, and "so"
         // applies too): with costs and weights >= +0 rounding is monotone, so c1, c2 >= vm, hence
         // fl(c1 + c2) >= vm and A = fl(fl(c1 + c2) - vm) >= +0; the vertical pass likewise
@@ -1159,7 +1216,7 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
                 {0, sm::CK_A, "sgm_ck_a01", 4.0 + ckb},
                 {0, sm::CK_B, "sgm_ck_b01", 8.0 + ckb},
                 {2, sm::CK_A, "sgm_ck_a23", 4.0 + ckb},
-                four ? Pass{2, sm::CK_B | sm::SGM_LAST, "sgm_last_wta", 8.0 + ckb + (p.keep_final_volume ? 4.0 : 0)}
+                four ? Pass{2, sm::CK_B | sm::SGM_LAST, "sgm_last_wta", 8.0 + ckb + (keep_final ? 4.0 : 0)}
                      : Pass{2, sm::CK_B | sm::CK_MID, "sgm_ck_b23", 12.0 + ckb}};
             for (const Pass& ps : passes) {
                 a.rv = RV[ps.path];
@@ -1205,7 +1262,7 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
             a.dir = i;
             int mode = (i == 0 ? sm::SGM_FIRST : 0) | (i == p.sgm_paths - 1 ? sm::SGM_LAST : 0);
             // algorithmic bytes per element: read C (+ read acc) (+ write acc | write final)
-            double per = 4.0 + ((mode & sm::SGM_FIRST) ? 0 : 4.0) + ((mode & sm::SGM_LAST) ? (p.keep_final_volume ? 4.0 : 0) : 4.0);
+            double per = 4.0 + ((mode & sm::SGM_FIRST) ? 0 : 4.0) + ((mode & sm::SGM_LAST) ? (keep_final ? 4.0 : 0) : 4.0);
             double bytes = (double)n * c->nvol * per + ((mode & sm::SGM_LAST) ? (double)n * c->npix * 2 : 0);
             const std::string name = std::string((mode & sm::SGM_LAST) ? "sgm_last_wta" : NAMES[i]) + sfx;
             sm_status s = timed(c, name.c_str(), bytes, [&] { sm::launch_sgm_path(a, mode, n, c->st); });
@@ -1228,12 +1285,13 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
         sm_status s = timed(c, name.c_str(), (double)n * c->nvol * (4.0 + 1.0 + (p.keep_final_volume ? 4.0 : 0)),
                             [&] { sm::launch_so(a, c->st); });
         if (s) return s;
-    } else {
+    } else if (!vmtop) {
         const std::string name = std::string("wta") + sfx;
         sm_status s = timed(c, name.c_str(), (double)n * c->nvol * 4.0 + (double)n * c->npix * 2,
                             [&] { sm::launch_wta(vm, disp, n, p.rows, p.cols, p.num_disparities, c->st); });
         if (s) return s;
     }
+    if (vmtop) return run_vmtop(c, n, view, B, vm, disp);
     return SM_OK;
 }
 
@@ -1842,10 +1900,45 @@ sm_status sm_get_volume(sm_ctx* c, int32_t view, float* dst) {
     if (c->stage < 2) return fail(c, SM_ESTATE, "no volume yet");
     float* src = view == 0 ? c->vm0 : (view == 1 ? c->vm1 : nullptr);
     if (!src) return fail(c, SM_EINVAL, view == 1 ? "right view not computed (compute_right_view = 0)" : "bad view");
-    if (c->stage >= 4 && !c->p.keep_final_volume && c->p.optimization == SM_OPT_SGM)
+    if (c->stage >= 4 && !c->p.keep_final_volume && !c->vt_on && c->p.optimization == SM_OPT_SGM)
         return fail(c, SM_ESTATE, "vm[view] after SGM is only kept with keep_final_volume = 1");
     HIP_TRY(c, hipMemcpyAsync(dst, src, c->nvol * 4, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
+
+sm_status sm_set_volume(sm_ctx* c, int32_t view, const float* src) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!src) return fail(c, SM_EINVAL, "null src");
+    if (c->stage < 2) return fail(c, SM_ESTATE, "sm_set_volume must follow sm_cost_calculate");
+    float* dst = view == 0 ? c->vm0 : (view == 1 ? c->vm1 : nullptr);
+    if (!dst) return fail(c, SM_EINVAL, view == 1 ? "right view not computed (compute_right_view = 0)" : "bad view");
+    HIP_TRY(c, hipMemcpyAsync(dst, src, c->nvol * 4, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    if (c->stage >= 4) c->stage = 3;   // dispOptimize may run (again) on the new volume
+    return SM_OK;
+}
+
+sm_status sm_get_top_disp(sm_ctx* c, int32_t view, float* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst || view < 0 || view > 1) return fail(c, SM_EINVAL, "bad arguments");
+    if (c->stage < 4 || !c->vt_tab || c->vt_ran_num[view] == 0 || c->vt_ran_num[view] != c->vt_num)
+        return fail(c, SM_ESTATE, "no candidate table of this view yet (sm_vmtop_config, then sm_disp_optimize / sm_run)");
+    const int M = c->vt_num;
+    std::vector<float> tab(c->npix * M * 2);
+    std::vector<int> cnt(c->npix);
+    HIP_TRY(c, hipMemcpyAsync(tab.data(), c->vt_tab + (size_t)view * c->cap * c->npix * M, tab.size() * 4, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->vt_cnt + (size_t)view * c->cap * c->npix, cnt.size() * 4, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    memset(dst, 0, c->npix * (size_t)(M + 1) * 2 * sizeof(float));
+    for (size_t i = 0; i < c->npix; i++) {
+        float* o = dst + i * (size_t)(M + 1) * 2;
+        const int n = cnt[i] < 0 ? 0 : (cnt[i] > M ? M : cnt[i]);
+        memcpy(o, tab.data() + i * M * 2, (size_t)n * 2 * sizeof(float));
+        o[(size_t)M * 2] = (float)cnt[i];
+    }
     return SM_OK;
 }
 
@@ -2396,6 +2489,45 @@ sm_status sm_aws_config(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gam
     c->aws_rv = radius_v;
     c->aws_ru = radius_u;
     c->aws_gamma = gamma_c;
+    return SM_OK;
+}
+
+sm_status sm_vmtop_config(sm_ctx* c, int32_t enable, int32_t method, int32_t num, float thres, int32_t ts, int32_t has_cir2,
+                          int32_t cir3_color_limit) {
+    if (!c) return SM_EINVAL;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (method < 0 || method > 2) return fail(c, SM_EINVAL, "method must be 0, 1 or 2 (vmTop_method)");
+    if (num < 1 || num > sm::VMTOP_MAX_NUM) return fail(c, SM_EINVAL, "num must be in [1, 8] (vmTop_Num)");
+    if (!std::isfinite(thres)) return fail(c, SM_EINVAL, "thres must be finite (vmTop_thres)");
+    if (enable && c->st) {   // a live context: size the tables for this num (first enable, or a larger num)
+        if (!sm::vmtop_shape_ok(c->p.rows, c->p.cols, c->p.num_disparities, c->cap))
+            return fail(c, SM_EINVAL, "sm_vmtop_config: rows * cols * batch_capacity too large");
+        if (num > c->vt_alloc_num) {
+            sm_status s = check(c);
+            if (s) return s;
+            HIP_TRY(c, hipStreamSynchronize(c->st));   // the old tables may still be read
+            const size_t views = (size_t)opt_views(c->p), cap = (size_t)c->cap;
+            if (c->vt_tab) hipFree(c->vt_tab);
+            c->vt_tab = nullptr;
+            c->vt_alloc_num = 0;
+            if ((s = dalloc(c, &c->vt_tab, views * cap * c->npix * num))) return s;
+            if (!c->vt_cnt && (s = dalloc(c, &c->vt_cnt, views * cap * c->npix))) return s;
+            if (!c->vt_tcnt && (s = dalloc(c, &c->vt_tcnt, cap * ((size_t)c->p.cols + 2 * (size_t)c->p.rows)))) return s;
+            c->vt_alloc_num = num;
+        } else if (num != c->vt_num) {
+            sm_status s = check(c);   // the table's stride changes: nothing queued may still write it
+            if (s) return s;
+            HIP_TRY(c, hipStreamSynchronize(c->st));
+        }
+    }
+    if (num != c->vt_num) c->vt_ran_num[0] = c->vt_ran_num[1] = 0;
+    c->vt_on = enable != 0 && c->st != nullptr;
+    c->vt_method = method;
+    c->vt_num = num;
+    c->vt_thres = thres;
+    c->vt_ts = ts;
+    c->vt_cir2 = has_cir2 != 0;
+    c->vt_color = cir3_color_limit != 0;
     return SM_OK;
 }
 

@@ -321,4 +321,25 @@ void launch_solve_all_pyr(const PyrArgs& a, hipStream_t st);
 void launch_median3(const int16_t* src, int16_t* dst, int n, int H, int W, hipStream_t st);
 int sgm_k_for(int D);
 
+// dispOptimize's Do_vmTop branch (sm_vmtop.hip): candidate selection and the three decision methods
+constexpr int VMTOP_MAX_NUM = 8;
+struct VmTopArgs {
+    const float* vm;            // [n][H][W][D] the volume dispOptimize would take the WTA of
+    float2* tab;                // [n][H][W][M] (disparity, cost) of the kept candidates, sorted by (cost, d)
+    int* cnt;                   // [n][H][W] candidates kept, 1 .. M
+    int* tcnt;                  // [n][W + 2 H] method 0: case-2 pixels per t = u + 2 v (zeroed before decide0_a)
+    const uint8_t* bgr;         // [n][2][H][W][3]; view 0 (I_c[0]) is read for both views
+    int16_t* disp;              // [n][H][W]
+    int H, W, D, M, n;
+    float thres;                // vmTop_thres
+    int method, ts, has_cir2, color_limit;
+};
+bool vmtop_shape_ok(int H, int W, int D, int n);
+void launch_vmtop_select(const VmTopArgs& a, hipStream_t st);
+void launch_vmtop_decide0_a(const VmTopArgs& a, hipStream_t st);   // writes -1 where case 2 is pending
+constexpr int VMTOP_RELAX_ROUNDS = 6;                              // launches of decide0_w before decide0_b
+void launch_vmtop_decide0_w(const VmTopArgs& a, hipStream_t st);   // pending pixels with no pending neighbour
+void launch_vmtop_decide0_b(const VmTopArgs& a, hipStream_t st);
+void launch_vmtop_decide12(const VmTopArgs& a, hipStream_t st);    // method 1 or 2
+
 }  // namespace sm

@@ -80,7 +80,14 @@ class StereoMatching:
             self.ts, self.disSc = ts, disSc
             self.errCsvName = errCsvName
             self.vmTop_Num = M
-            self.vmTop_thres = lamc * 0.01
+            self.vmTop_thres = float(np.float32(lamc * 0.01))   # (float)(lamc_ * 0.01): double product (h:323)
+            # dispOptimize's candidate-disparity selection (h:182-188, 320-326; sm_vmtop_config); read when
+            # the object is constructed
+            self.Do_vmTop = False
+            self.vmTop_method = 0
+            self.vmTop_thres_dirNum = 8                # carried; genDispFromTopCostVm2 does not read it
+            self.vmTop_hasCir2 = True
+            self.vmTop_cir3_doColorLimit = False
             self.rows, self.cols = h, w
             self.LRmaxDiff = 0.0                       # h:212
             self.DISP_OCC = -2 * 16                    # h:216
@@ -166,6 +173,10 @@ class StereoMatching:
         if self.aggregation == "GFNL":
             st = self._lib.sm_gfnl_config(ctx, float(self.GFNL_VAR_THRESH))
             _capi.check(self._lib, ctx, st, "sm_gfnl_config")
+        if param.Do_vmTop:
+            st = self._lib.sm_vmtop_config(ctx, 1, int(param.vmTop_method), int(param.vmTop_Num), float(param.vmTop_thres),
+                                           int(param.ts), int(param.vmTop_hasCir2), int(param.vmTop_cir3_doColorLimit))
+            _capi.check(self._lib, ctx, st, "sm_vmtop_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -434,6 +445,22 @@ class StereoBatch:
         """sm_gfnl_config: "GFNL"'s variance threshold (any finite value), from the next run on."""
         st = self._lib.sm_gfnl_config(self._ctx, float(var_thresh))
         _capi.check(self._lib, self._ctx, st, "gfnl_config")
+
+    def vmtop_config(self, enable: bool = True, method: int = 0, num: int = 2, thres: float = 1.09, ts: int = 10,
+                     has_cir2: bool = True, cir3_color_limit: bool = False):
+        """sm_vmtop_config: dispOptimize's Do_vmTop branch (candidate-disparity selection instead of the
+        plain WTA after "sgm" / ""), from the next run on; num in [1, 8], method 0, 1 or 2."""
+        st = self._lib.sm_vmtop_config(self._ctx, int(bool(enable)), int(method), int(num), float(thres), int(ts),
+                                       int(bool(has_cir2)), int(bool(cir3_color_limit)))
+        _capi.check(self._lib, self._ctx, st, "vmtop_config")
+        self._vmtop_num = int(num)
+
+    def get_top_disp(self, view: int = 0) -> np.ndarray:
+        """sm_get_top_disp: the first pair's candidate table [H][W][num + 1][2] of the last run with vmTop on
+        (num as given to vmtop_config)."""
+        out = np.empty((self.shape[0], self.shape[1], getattr(self, "_vmtop_num", 2) + 1, 2), np.float32)
+        _capi.check(self._lib, self._ctx, self._lib.sm_get_top_disp(self._ctx, view, _capi.ptr(out)), "get_top_disp")
+        return out
 
     def set_schedule(self, num_streams: int = 0, sub_batch: int = 0):
         """sm_set_schedule: num_streams / sub_batch for the following runs on the same allocations

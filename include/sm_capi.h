@@ -29,6 +29,9 @@
  *   sm_vmtop_config    <- Parameters::Do_vmTop, vmTop_* and ts       stereoMatching.h:182-188, 201, 320-326
  *                         (dispOptimize cpp:1108-1128, selectTopCostFromVolumn h:2405-2461,
  *                          genDispFromTopCostVm2 cpp:1514-1885)
+ *   sm_cbca_double_config <- Parameters::cbca_double_win, cbca_crossL[1] ..  stereoMatching.h:144, 263-275
+ *                         (CBCA cpp:4333-4360, combine2Vm_4 cpp:4273-4331)
+ *   sm_get_cbca_dw_mask <- member arm_Mask as combine2Vm_4 leaves it (cpp:4303-4318)
  *   sm_get_volume / sm_set_volume <- public member vm[view]       stereoMatching.h:2720
  *   sm_get_arms        <- public member HVL[view]                    stereoMatching.h:2717
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
@@ -368,7 +371,29 @@ SM_API sm_status sm_set_volume(sm_ctx* ctx, int32_t view, const float* src);
  * entries the reference never writes read as 0. */
 SM_API sm_status sm_get_top_disp(sm_ctx* ctx, int32_t view, float* dst);
 
+/* CBCA()'s double-window branch (Parameters::cbca_double_win, cpp:4337-4357).  With it on, "CBCA" aggregates the
+ * raw costs twice -- with the arms of window 1 (arm_l2 = cbca_crossL[1], arm_l_out2 = cbca_crossL_out[1],
+ * arm_c_thresh2 = cbca_cTresh[1], arm_c_thresh_out2 = cbca_cTresh_out[1]; 23, 23, 30, 0 in the reference) into a
+ * second volume, and with sm_params' window 0 in place -- and combine2Vm_4 (cpp:4273-4331) gives a pixel all its
+ * costs from the window-1 volume where the 3 x 3 normalised box mean (BORDER_REFLECT_101) of "the longest of the
+ * four window-0 arms" is < arm_len_thres (the literal 5 of cpp:4297).  As in the reference: both runs do two
+ * iterations whatever cbca_iterations says (cbca_core(.., 2)); the mask comes from the LEFT image's arms for
+ * both views (HVL[0]); window 0's arms are computed last, so sm_get_arms and refine() see them as without the
+ * switch; arm_min_l applies to both windows.  Not sm_params fields (the struct keeps its size): off by default,
+ * takes effect from the next sm_cost_calculate / sm_run.  The maps are the same for every schedule.  The second
+ * arm planes, one second volume and the mask are allocated on the first enabling call (batch_capacity pairs);
+ * a context that has had the switch on runs no placement trials.  SM_EINVAL, with the argument named in
+ * sm_last_error, on a context whose aggregation is not SM_AGG_CBCA, for arm_l2 < 0, arm_l_out2 outside [0, 84],
+ * a negative threshold or an arm_len_thres that is not finite; the arguments are checked without a device.
+ * (Parameters::GF_double_win has no entry point: both arms of the reference's branch run guideFilter(0, vm),
+ * cpp:4406-4418, so the facades accept the field and pass nothing on.) */
+SM_API sm_status sm_cbca_double_config(sm_ctx* ctx, int32_t enable, int32_t arm_l2, int32_t arm_l_out2,
+                                       int32_t arm_c_thresh2, int32_t arm_c_thresh_out2, float arm_len_thres);
+
 /* Diagnostics used by the parity tests. */
+/* CBCA's double window: pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where
+ * vm[view] holds the window-1 costs). */
+SM_API sm_status sm_get_cbca_dw_mask(sm_ctx* ctx, uint8_t* dst);
 /* "GFNL": pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where the variance
  * is below the threshold, i.e. where vm[0] is NL's value alone). */
 SM_API sm_status sm_get_gfnl_mask(sm_ctx* ctx, uint8_t* dst);

@@ -364,7 +364,18 @@ class StereoMatching {
         std::string errCsvName;
         int censusFunc = 3;                   // h:244
         int cbca_iterationNum = 2, cbca_minArmL = 1;
-        int cbca_crossL0 = 17, cbca_crossL_out0 = 34, cbca_cTresh0 = 20, cbca_cTresh_out0 = 6;
+        // the three cross windows (h:140-143, 263-274).  Index 0 is CBCA's window; index 1 is the second window
+        // of the double-window branch; index 2 is carried (no code path of the hot path reads it)
+        unsigned char cbca_crossL[3] = {17, 23, 34};
+        unsigned char cbca_crossL_out[3] = {34, 23, 34};
+        unsigned char cbca_cTresh[3] = {20, 30, 30};
+        unsigned char cbca_cTresh_out[3] = {6, 0, 0};
+        // CBCA()'s double-window branch (h:144, 275; cpp:4337-4357; sm_cbca_double_config): set before the object
+        // is constructed.  Both aggregations then do two iterations whatever cbca_iterationNum says.
+        bool cbca_double_win = false;
+        // GF()'s double-window switch (h:145, 276): both arms of the reference's branch run guideFilter(0, vm)
+        // (cpp:4406-4418), so the field is accepted and changes nothing
+        bool GF_double_win = false;
         int sgm_scanNum = 4, sgm_corDifThres = 15, sgm_reduCoeffi1 = 4;
         int errorThreshold = 1;               // h:225
         float LRmaxDiff = 0;                  // h:212
@@ -530,10 +541,10 @@ class StereoMatching {
         p.lam_cen = (float)param.lamCen;
         p.lam_g = (float)param.lamG;
         const int sc = param.disSc > 1 ? param.disSc : 1;   // calArms: L / scale (cpp:5367-5371)
-        p.arm_l = param.cbca_crossL0 / sc;
-        p.arm_l_out = param.cbca_crossL_out0 / sc;
-        p.arm_c_thresh = param.cbca_cTresh0;
-        p.arm_c_thresh_out = param.cbca_cTresh_out0;
+        p.arm_l = param.cbca_crossL[0] / sc;
+        p.arm_l_out = param.cbca_crossL_out[0] / sc;
+        p.arm_c_thresh = param.cbca_cTresh[0];
+        p.arm_c_thresh_out = param.cbca_cTresh_out[0];
         p.arm_min_l = param.cbca_minArmL;
         p.cbca_iterations = param.cbca_iterationNum;
         p.sgm_paths = param.sgm_scanNum;
@@ -558,6 +569,10 @@ class StereoMatching {
             check(sm_vmtop_config(ctx_, 1, param.vmTop_method, param.vmTop_Num, param.vmTop_thres, param.ts,
                                   param.vmTop_hasCir2 ? 1 : 0, param.vmTop_cir3_doColorLimit ? 1 : 0),
                   "sm_vmtop_config");
+        if (param.cbca_double_win && aggregation == "CBCA")   // armLthres = 5 (cpp:4297)
+            check(sm_cbca_double_config(ctx_, 1, param.cbca_crossL[1] / sc, param.cbca_crossL_out[1] / sc, param.cbca_cTresh[1],
+                                        param.cbca_cTresh_out[1], 5.0f),
+                  "sm_cbca_double_config");
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }
     void check(sm_status s, const char* what) {

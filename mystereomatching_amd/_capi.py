@@ -22,6 +22,7 @@ FIF_IMPROVE, FIF_PLAIN = 0, 1
 AWS_DEFAULTS = (17, 17, 5.0)   # radius_v, radius_u, gamma_c (sm_aws_config)
 BF_DEFAULTS = (12, 12)         # ksize_v, ksize_u (sm_bf_config)
 GFNL_VAR_THRESH = 400.0        # sm_gfnl_config
+CBCA_DW_DEFAULTS = (23, 23, 30, 0, 5.0)   # arm_l2, arm_l_out2, arm_c_thresh2, arm_c_thresh_out2, arm_len_thres
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -109,6 +110,8 @@ SIGNATURES = [
     ("sm_vmtop_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32]),
     ("sm_set_volume", C.c_int, [_P, C.c_int32, _P]),
     ("sm_get_top_disp", C.c_int, [_P, C.c_int32, _P]),
+    ("sm_cbca_double_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
+    ("sm_get_cbca_dw_mask", C.c_int, [_P, _P]),
 ]
 
 _lib = None

@@ -107,6 +107,20 @@ struct sm_ctx {
     int* vt_tcnt = nullptr;        // [cap][cols + 2 rows]
     int vt_alloc_num = 0;          // candidates per pixel the table is sized for
     int vt_ran_num[2] = {0, 0};    // vt_num of the last selection on each view (0: none), for sm_get_top_disp
+    // CBCA()'s double-window branch (sm_cbca_double_config): window 1's arm settings and combine2Vm_4's
+    // threshold, window 1's arm planes (laid out and padded like `arms`, for their own lag), the large-window
+    // volume and arm_Mask.  One second volume serves both views: the views run one after the other on the
+    // group's stream, and view 0's selection has read it before view 1's large-window run writes it.
+    bool dw_on = false;
+    int dw_l = 23, dw_l_out = 23, dw_ct = 30, dw_ct_out = 0;
+    int dw_isum = 45;              // arm_Mask = sum of the nine arm maxima < dw_isum: armLthres' integer form (dw_int_threshold)
+    uint8_t* arms2 = nullptr;      // [cap][2 views][2 planes][npix] u32
+    uint8_t* arms2_alloc = nullptr;
+    size_t arms2_bytes = 0;
+    int arms2_lag = -1;            // the lag arms2's pads are sized for
+    float* vm2 = nullptr;          // [cap][npix][D] + the volumes' tail pad
+    uint8_t* dw_mask = nullptr;    // [cap][npix]
+    bool dw_ran = false;           // the mask holds the last sm_cost_calculate / sm_run's choice
     // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -299,6 +313,22 @@ bool bf_exact(const sm_params& p) {
 }
 
 int cbca_lag(const sm_params& p) { return p.arm_l_out > p.arm_min_l ? p.arm_l_out : p.arm_min_l; }
+// the double window's second arm set (window 1): its own maximum arm length
+int cbca_lag2(const sm_ctx* c) { return c->dw_l_out > c->p.arm_min_l ? c->dw_l_out : c->p.arm_min_l; }
+// cbca_core's iteration count: the double-window branch passes a literal 2 (cpp:4344, 4347) and never
+// reads cbca_iterations
+int cbca_iters(const sm_ctx* c) { return c->dw_on ? 2 : c->p.cbca_iterations; }
+
+// combine2Vm_4's predicate on the nine-term sum s of integer arm maxima is boxFilter's (float)(s * (1.0 / 9))
+// (double sums, one rounding) < thres.  The product and its rounding are non-decreasing in s, so for every
+// finite thres the predicate is `s < t` with t the first sum that fails it; the scan covers every sum the arm
+// kernel can produce (arms <= 84: s <= 756) and so is the proof of the equivalence for the threshold at hand.
+// The reference's 5.0f gives 45: s = 45 yields exactly 5.0f and is not selected.
+int dw_int_threshold(float thres) {
+    int t = 0;
+    while (t <= 9 * 84 && (float)((double)t * (1.0 / 9)) < thres) t++;
+    return t;
+}
 
 // Every dividend of iteration k's normalisation (genfinalVm_cbca, cpp:3969-3992) is 0 or
 // >= 2^-110, so the area division needs no check for tiny dividends (sm_device.h div_area)?
@@ -492,7 +522,8 @@ void free_all(sm_ctx* c) {
                     c->nl_table, c->nl_val, c->nl_oup, c->nl_ofin, c->nl_par, c->nl_best, c->nl_mst, c->nl_adj, c->nl_walk,
                     c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w,
                     c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3],
-                    c->bf_rs, c->gfnl_res, c->gfnl_mask, c->vt_tab, c->vt_cnt, c->vt_tcnt};
+                    c->bf_rs, c->gfnl_res, c->gfnl_mask, c->vt_tab, c->vt_cnt, c->vt_tcnt,
+                    c->arms2_alloc, c->vm2, c->dw_mask};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -593,6 +624,33 @@ sm_status run_prep(sm_ctx* c, int n, const Bufs& B) {
     const int H = p.rows, W = p.cols;
     const bool census = needs_census(p), arms = needs_arms(p);
     const bool flags = p.optimization == SM_OPT_SGM;
+    if (c->dw_on) {
+        // window 1's arms first (calArms with cbca_crossL[1] .., cpp:4343), through the same arm kernels into
+        // their own planes; the pass below then leaves the arm-walk planes as window 0 wrote them
+        sm::PrepArgs a{};
+        a.gray = B.gray;
+        a.bgr = B.bgr;
+        a.px = B.px;
+        a.pxh = B.pxh;
+        a.pxv = B.pxv;
+        a.code = B.code;
+        a.arms = c->arms2 + (size_t)(B.arms - c->arms);
+        a.flags = B.flags;
+        a.H = H;
+        a.W = W;
+        a.rv = p.census_rv;
+        a.ru = p.census_ru;
+        a.ring = p.census_ring;
+        a.L = c->dw_l;
+        a.L_out = c->dw_l_out;
+        a.C_D = c->dw_ct;
+        a.C_D_out = c->dw_ct_out;
+        a.minL = p.arm_min_l;
+        a.cor_thres = p.sgm_cor_dif_thres;
+        a.do_arms = 1;
+        sm_status s = timed(c, "prep_dw", (double)n * 2 * c->npix * (3 + 8), [&] { sm::launch_prep(a, n, c->st); });
+        if (s) return s;
+    }
     {
         sm::PrepArgs a{};
         a.gray = B.gray;
@@ -632,10 +690,12 @@ sm_status run_prep(sm_ctx* c, int n, const Bufs& B) {
 bool cost_scan_fused(const sm_ctx* c, int view) {
     const sm_params& p = c->p;
     const int cw = (census_len(p) + 31) / 32;
-    return c->fuse_cost_scan && p.aggregation == SM_AGG_CBCA && p.cbca_iterations > 0 && view < n_views(p) &&
+    // (the double window runs the sweep once per arm set: the longer lag decides)
+    const int lag = c->dw_on ? std::max(cbca_lag(p), cbca_lag2(c)) : cbca_lag(p);
+    return c->fuse_cost_scan && p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0 && view < n_views(p) &&
            p.cost_method == SM_COST_CENSUS_GRAD && cw >= 3 && p.lam_g == 1.0f &&
            sm::cost_nosel_ok(p.grad_trunc, p.lam_g, (float)census_len(p)) &&
-           sm::cbca_hsc_smem_bytes(cbca_lag(p), cw) <= 64 * 1024;
+           sm::cbca_hsc_smem_bytes(lag, cw) <= 64 * 1024;
 }
 
 sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
@@ -684,31 +744,36 @@ sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
                  [&] { sm::launch_cost(a, m, n, c->st); });
 }
 
-sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B) {
+// One cbca_core run on a view.  win 0: the view's volume with the window-0 arms (the only run without the
+// double window).  win 1: the double window's large-window run, on the second volume with window 1's arms,
+// lag and ring size; it records none of the group's events (the window-0 run that follows reads the same
+// inputs last).
+sm_status run_cbca_core(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B, int win) {
     // cbca_core (cpp:5585-5666): iteration k runs H then V for even k, V then H for odd k.
     // The last pass of iteration k and the first pass of iteration k+1 share a direction and
     // are fused into one CB_NORM_SCAN sweep, so N iterations take N + 1 sweeps.
     const sm_params& p = c->p;
-    const int N = p.cbca_iterations;
+    const int N = cbca_iters(c);
     if (N <= 0) return SM_OK;
+    const size_t pair_off = (size_t)(B.vm0 - c->vm0);   // floats from the allocation base to the group's first pair
     sm::CbcaArgs a{};
-    a.vm = view == 0 ? B.vm0 : B.vm1;
+    a.vm = win ? c->vm2 + pair_off : (view == 0 ? B.vm0 : B.vm1);
     a.view = view;
     a.dummy = c->dummy;
-    a.arms = (const uint32_t*)B.arms;
+    a.arms = (const uint32_t*)(win ? c->arms2 + (size_t)(B.arms - c->arms) : B.arms);
     a.H = p.rows;
     a.W = p.cols;
     a.D = p.num_disparities;
-    a.lag = cbca_lag(p);
-    a.vm_end = (view == 0 ? c->vm0 : c->vm1) + (size_t)c->cap * c->nvol + c->vtail;   // incl. the tail pad
-    a.arms_end = (const uint32_t*)(c->arms + c->arms_bytes);
+    a.lag = win ? cbca_lag2(c) : cbca_lag(p);
+    a.vm_end = (win ? c->vm2 : (view == 0 ? c->vm0 : c->vm1)) + (size_t)c->cap * c->nvol + c->vtail;   // incl. the tail pad
+    a.arms_end = (const uint32_t*)(win ? c->arms2 + c->arms2_bytes : c->arms + c->arms_bytes);
     a.scale = w;
     a.apply_scale = 0;
     a.num_cu = c->num_cu;
-    a.arm_pad_rows = 2 * cbca_lag(p);
+    a.arm_pad_rows = 2 * a.lag;
     const double bytes = (double)n * c->nvol * 8.0;
-    // profile names: "cbca_h_scan" etc. for vm[0], "cbca_h_scan_r" etc. for vm[1]
-    std::string sfx = view == 0 ? "" : "_r";
+    // profile names: "cbca_h_scan" etc. for vm[0], "cbca_h_scan_r" etc. for vm[1]; "_dw" for the large window
+    std::string sfx = std::string(view == 0 ? "" : "_r") + (win ? "_dw" : "");
     auto nm = [&](const char* base) { static thread_local std::string t; t = std::string(base) + sfx; return t.c_str(); };
     sm_status s;
     if (cost_scan_fused(c, view)) {   // the costs are computed in the sweep: it only writes the volume
@@ -719,16 +784,18 @@ sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const B
         a.grad_trunc = p.grad_trunc;
         a.grad_adaptive = p.grad_adaptive;
         a.cwords = (census_len(p) + 31) / 32;
+        // grad() built its adaptive weights from window 0's arms (cpp:630-633), before CBCA() made window 1's
+        a.cost_arms = win ? (const uint32_t*)B.arms : nullptr;
         s = timed(c, nm("cbca_h_scan_cost"), (double)n * c->nvol * 4.0, [&] { sm::launch_cbca_hsc(a, n, c->st); });
     } else {
         s = timed(c, nm("cbca_h_scan"), bytes, [&] { sm::launch_cbca(a, true, sm::CB_SCAN, n, c->st); });
     }
     if (s) return s;
-    if (c->in_ev && view == n_views(p) - 1) {   // the last sweep that reads the group's input images
+    if (!win && c->in_ev && view == n_views(p) - 1) {   // the last sweep that reads the group's input images
         HIP_TRY(c, hipEventRecord(c->in_ev, c->st));
         c->in_ev = nullptr;
     }
-    if (c->stagger_ev) {   // the next group may start: this group's next sweep is LDS- and issue-bound
+    if (!win && c->stagger_ev) {   // the next group may start: this group's next sweep is LDS- and issue-bound
         HIP_TRY(c, hipEventRecord(c->stagger_ev, c->st));
         c->stagger_ev = nullptr;
     }
@@ -752,6 +819,48 @@ sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const B
         if (s) return s;
     }
     return SM_OK;
+}
+
+// CBCA() on one view (cpp:4333-4360).  With the double window: the large-window run on a second volume that
+// starts from the same raw costs (its own fused first scan where the costs are computed in the sweep -- with
+// window 0's arms for the gradient term's weights, as grad() computed them -- else one device copy of the raw
+// volume), the window-0 run in place, then combine2Vm_4: the mask from the LEFT image's window-0 arms (made
+// once, with view 0) and the selection.  SolveAll's weight is fused into the last normalising pass of both
+// runs: every element of the composed volume is one of the two runs' elements, and scaling an element commutes
+// with choosing it, so the result equals "compose, then scale" bit for bit.
+sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B) {
+    if (!c->dw_on) return run_cbca_core(c, n, view, fuse_scale, w, B, 0);
+    const sm_params& p = c->p;
+    const size_t pair_off = (size_t)(B.vm0 - c->vm0);
+    sm_status s;
+    if (!cost_scan_fused(c, view)) {
+        const float* raw = view == 0 ? B.vm0 : B.vm1;
+        float* dst = c->vm2 + pair_off;
+        const size_t bytes = (size_t)n * c->nvol * 4;
+        hipError_t e = hipSuccess;
+        s = timed(c, view == 0 ? "dw_copy_raw" : "dw_copy_raw_r", 2.0 * bytes,
+                  [&] { e = hipMemcpyAsync(dst, raw, bytes, hipMemcpyDeviceToDevice, c->st); });
+        if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync (raw costs for the large window)");
+        if (s) return s;
+    }
+    if ((s = run_cbca_core(c, n, view, fuse_scale, w, B, 1))) return s;
+    if ((s = run_cbca_core(c, n, view, fuse_scale, w, B, 0))) return s;
+    sm::DwArgs a{};
+    a.arms = (const uint32_t*)B.arms;
+    a.mask = c->dw_mask;
+    a.vm = view == 0 ? c->vm0 : c->vm1;
+    a.vm2 = c->vm2;
+    a.pix0 = pair_off / (size_t)p.num_disparities;
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.isum = c->dw_isum;
+    if (view == 0) {
+        if ((s = timed(c, "dw_mask", (double)n * c->npix * 9.0, [&] { sm::launch_dw_mask(a, n, c->st); }))) return s;
+        c->dw_ran = true;
+    }
+    // (algorithmic bytes: the mask; the volume traffic is 8 B per selected element, known only from the mask)
+    return timed(c, view == 0 ? "dw_select" : "dw_select_r", (double)n * c->npix, [&] { sm::launch_dw_select(a, n, c->st); });
 }
 
 sm_status run_scale(sm_ctx* c, int n, int view, float w, const Bufs& B) {
@@ -2021,7 +2130,7 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     // a pipeline start staggers group 1 (after group 0's CBCA); every other entry point joins
     // first (check -> join_all), and the asynchronous map copy waits for both groups.
     const bool piped = c->pipelined && ns == 2 && n >= 2 && (n + g - 1) / g == 2;
-    const bool early = !piped && SM_STAGGER_STAGE == 1 && c->p.aggregation == SM_AGG_CBCA && c->p.cbca_iterations > 0;
+    const bool early = !piped && SM_STAGGER_STAGE == 1 && c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0;
     // (a different split of the pairs would let the groups of two calls share a pair: join first)
     if ((!piped || g != c->pipe_g) && (s = join_all(c))) return s;
     const bool start = !(piped && c->pipe_live);   // groups start from a joined state
@@ -2069,7 +2178,7 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
         }
         if (ns > 1 && early) c->stagger_ev = c->xev[1 + k % 8];
         for (int v = 0; v < n_views(c->p) && !s_out && !pipe; v++) {
-            if (c->p.aggregation == SM_AGG_CBCA && c->p.cbca_iterations > 0)
+            if (c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0)
                 s_out = run_cbca(c, m2, v, true, w, B);   // SolveAll fused into the last pass
             else if (!SM_FUSE_SOLVE_ALL || !(c->p.aggregation == SM_AGG_GF || c->p.aggregation == SM_AGG_FIF ||
                                              c->p.aggregation == SM_AGG_AWS || c->p.aggregation == SM_AGG_BF ||
@@ -2559,6 +2668,66 @@ sm_status sm_get_gfnl_mask(sm_ctx* c, uint8_t* dst) {
     if (c->p.aggregation != SM_AGG_GFNL) return fail(c, SM_EINVAL, "sm_get_gfnl_mask: the context's aggregation is not SM_AGG_GFNL");
     if (c->stage < 2) return fail(c, SM_ESTATE, "no mask yet");
     HIP_TRY(c, hipMemcpyAsync(dst, c->gfnl_mask, c->npix, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
+
+sm_status sm_cbca_double_config(sm_ctx* c, int32_t enable, int32_t arm_l2, int32_t arm_l_out2, int32_t arm_c_thresh2,
+                                int32_t arm_c_thresh_out2, float arm_len_thres) {
+    if (!c) return SM_EINVAL;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (c->p.aggregation != SM_AGG_CBCA)
+        return fail(c, SM_EINVAL, "sm_cbca_double_config: the context's aggregation is not SM_AGG_CBCA");
+    if (arm_l2 < 0) return fail(c, SM_EINVAL, "arm_l2 must be >= 0 (cbca_crossL[1])");
+    if (arm_l_out2 < 0 || arm_l_out2 > 84) return fail(c, SM_EINVAL, "arm_l_out2 must be in [0, 84] (cbca_crossL_out[1])");
+    if (arm_c_thresh2 < 0) return fail(c, SM_EINVAL, "arm_c_thresh2 must be >= 0 (cbca_cTresh[1])");
+    if (arm_c_thresh_out2 < 0) return fail(c, SM_EINVAL, "arm_c_thresh_out2 must be >= 0 (cbca_cTresh_out[1])");
+    if (!std::isfinite(arm_len_thres)) return fail(c, SM_EINVAL, "arm_len_thres must be finite (armLthres)");
+    const bool on = enable != 0 && c->st != nullptr;
+    if (c->st) {   // a live context: nothing queued may still use the old settings' buffers
+        sm_status s = check(c);
+        if (s) return s;
+        const int lag2 = arm_l_out2 > c->p.arm_min_l ? arm_l_out2 : c->p.arm_min_l;
+        if (on && (!c->vm2 || lag2 != c->arms2_lag)) {
+            HIP_TRY(c, hipStreamSynchronize(c->st));
+            c->dw_on = false;   // (stays off if an allocation below fails)
+            const size_t cap = (size_t)c->cap, cols = (size_t)c->p.cols;
+            if (c->arms2_alloc) hipFree(c->arms2_alloc);
+            c->arms2_alloc = c->arms2 = nullptr;
+            c->arms2_lag = -1;
+            // the first arm set's layout: a zeroed front pad of 2 lag rows and tail pad of 2 lag + 64 rows
+            const size_t pad = (2 * (size_t)lag2 * cols * 4 + 255) / 256 * 256;
+            const size_t tail = (size_t)(2 * lag2 + 64) * cols * 4;
+            c->arms2_bytes = cap * 2 * 2 * c->npix * 4;
+            if ((s = dalloc(c, &c->arms2_alloc, pad + c->arms2_bytes + tail))) return s;
+            c->arms2 = c->arms2_alloc + pad;
+            HIP_TRY(c, hipMemset(c->arms2_alloc, 0, pad));
+            HIP_TRY(c, hipMemset(c->arms2 + c->arms2_bytes, 0, tail));
+            c->arms2_lag = lag2;
+            if (!c->vm2 && (s = dalloc(c, &c->vm2, cap * c->nvol + c->vtail))) return s;
+            if (!c->dw_mask && (s = dalloc(c, &c->dw_mask, cap * c->npix))) return s;
+        }
+        // placement trials time one volume set against another; the second volume is not part of a set, so
+        // a context that has had the double window on chooses no placement (the maps are the same either way)
+        if (on) c->place_trials = 0;
+    }
+    c->dw_on = on;
+    c->dw_ran = false;
+    c->dw_l = arm_l2;
+    c->dw_l_out = arm_l_out2;
+    c->dw_ct = arm_c_thresh2;
+    c->dw_ct_out = arm_c_thresh_out2;
+    c->dw_isum = dw_int_threshold(arm_len_thres);
+    return SM_OK;
+}
+
+sm_status sm_get_cbca_dw_mask(sm_ctx* c, uint8_t* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst) return fail(c, SM_EINVAL, "null dst");
+    if (!c->dw_on || !c->dw_ran || c->stage < 2)
+        return fail(c, SM_ESTATE, "no mask yet (sm_cbca_double_config, then sm_cost_calculate / sm_run)");
+    HIP_TRY(c, hipMemcpyAsync(dst, c->dw_mask, c->npix, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     return SM_OK;
 }

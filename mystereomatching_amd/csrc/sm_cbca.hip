@@ -1613,7 +1613,8 @@ __global__ __launch_bounds__(64 * (1 + HSC_NCW)) void k_cbca_hsc(const CbcaArgs 
     const uint8_t* grayM = a.gray + ((size_t)b * 2 + mview) * npix;
     const hsc_u4* codeF = (const hsc_u4*)(a.code + ((size_t)b * 2 + fview) * npix + (size_t)v * W);
     const hsc_u4* codeM = (const hsc_u4*)(a.code + ((size_t)b * 2 + mview) * npix + (size_t)v * W);
-    const uint32_t* armF = a.arms + ((size_t)b * 4 + fview * 2) * npix + (size_t)v * W;
+    // (the weights' arms are the cost measure's own, window 0's, also where the sweep aggregates with another set)
+    const uint32_t* armF = (a.cost_arms ? a.cost_arms : a.arms) + ((size_t)b * 4 + fview * 2) * npix + (size_t)v * W;
     const int icd = (int)a.census_default;
     uint32_t* cw = (uint32_t*)hsc_smem + hsc_base_words(a.lag);
     hsc_u4* recA = (hsc_u4*)cw;                      // [2 RR]
@@ -1899,6 +1900,11 @@ void launch_cbca(const CbcaArgs& a, bool horiz, int mode, int n, hipStream_t st)
 }
 
 }  // namespace sm
+
+// CBCA()'s double-window branch (cbca_double_win: the mask and the selection of combine2Vm_4) is part of this
+// translation unit: the host-side sanitizer build of the C ABI (tests/test_sanitizers.py) links a fixed list of
+// kernel objects, so a new launcher has to live in one of them.
+#include "sm_cbca_dw.hip"
 
 #if SM_CB_NSV_TRACE
 // diagnostic builds only: [block][wave][phase] cycle sums of the last NsV2 launch (phase 7 = tiles)

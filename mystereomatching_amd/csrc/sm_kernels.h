@@ -73,6 +73,8 @@ struct CbcaArgs {
     float census_default, grad_trunc;
     int grad_adaptive;
     int cwords;                 // 32-bit census words in use: 3 or 4
+    const uint32_t* cost_arms;  // the arm planes the gradient term's adaptive weights read, where they are not
+                                // `arms` (the double window's second run: grad() saw window 0's); nullptr: `arms`
 };
 constexpr int CBCA_VM_TAIL_ROWS = 8;   // volume tail pad in rows of W * D floats (fast V sweeps)
 
@@ -341,5 +343,19 @@ constexpr int VMTOP_RELAX_ROUNDS = 6;                              // launches o
 void launch_vmtop_decide0_w(const VmTopArgs& a, hipStream_t st);   // pending pixels with no pending neighbour
 void launch_vmtop_decide0_b(const VmTopArgs& a, hipStream_t st);
 void launch_vmtop_decide12(const VmTopArgs& a, hipStream_t st);    // method 1 or 2
+
+// CBCA()'s double-window branch (sm_cbca_dw.hip): combine2Vm_4's mask and selection
+struct DwArgs {
+    const uint32_t* arms;       // window-0 arm planes of the launch's first pair: [n][view][plane][H][W]
+    uint8_t* mask;              // arm_Mask of every pair the context holds (allocation base): [cap][H][W]
+    float* vm;                  // the view's volume, allocation base (16-byte aligned): [cap][H][W][D]
+    const float* vm2;           // the large-window volume, allocation base: [cap][H][W][D]
+    size_t pix0;                // first pixel of the launch: first pair * H * W
+    int H, W, D;
+    int isum;                   // arm_Mask = sum of the nine maxima < isum: armLthres (cpp:4297) in the integer
+                                // form the host derives for it (dw_int_threshold, sm_capi.cpp)
+};
+void launch_dw_mask(const DwArgs& a, int n, hipStream_t st);     // H, W >= 2
+void launch_dw_select(const DwArgs& a, int n, hipStream_t st);
 
 }  // namespace sm

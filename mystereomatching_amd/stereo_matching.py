@@ -72,6 +72,12 @@ class StereoMatching:
             self.cbca_crossL_out = [34, 23, 34]        # h:266-268
             self.cbca_cTresh = [20, 30, 30]            # h:269-271
             self.cbca_cTresh_out = [6, 0, 0]           # h:272-274
+            # CBCA()'s double-window branch (h:144, 275; cpp:4337-4357; sm_cbca_double_config): window 1 is
+            # index 1 of the four lists above; read when the object is constructed
+            self.cbca_double_win = False
+            # GF()'s switch (h:145, 276): both arms of the reference's branch run guideFilter(0, vm)
+            # (cpp:4406-4418), so the field is accepted and changes nothing
+            self.GF_double_win = False
             self.sgm_scanNum = 4                       # h:236 (the reference hard-codes 4, cpp:6214)
             self.sgm_P1, self.sgm_P2 = 1.0, 3.0        # ctor override for CBCA (cpp:2089-2091)
             self.sgm_corDifThres = 15                  # h:239
@@ -130,6 +136,13 @@ class StereoMatching:
             p.lr_consis = int(lr_consis)
             return p
 
+        def cbca_double_args(self):
+            """sm_cbca_double_config's arguments after `enable`: window 1 (calArms divides its arm limits by
+            the level's scale too, cpp:5367-5371) and combine2Vm_4's armLthres = 5 (cpp:4297)."""
+            sc = self.disSc if self.disSc > 1 else 1
+            return (int(self.cbca_crossL[1] / sc), int(self.cbca_crossL_out[1] / sc), int(self.cbca_cTresh[1]),
+                    int(self.cbca_cTresh_out[1]), _capi.CBCA_DW_DEFAULTS[4])
+
     def __init__(self, I1_c, I2_c, I1_g, I2_g, DT=None, all_mask=None, nonocc_mask=None, disc_mask=None,
                  param: Optional["StereoMatching.Parameters"] = None, device: int = 0,
                  keep_final_volume: bool = False):
@@ -177,6 +190,9 @@ class StereoMatching:
             st = self._lib.sm_vmtop_config(ctx, 1, int(param.vmTop_method), int(param.vmTop_Num), float(param.vmTop_thres),
                                            int(param.ts), int(param.vmTop_hasCir2), int(param.vmTop_cir3_doColorLimit))
             _capi.check(self._lib, ctx, st, "sm_vmtop_config")
+        if param.cbca_double_win and self.aggregation == "CBCA":
+            st = self._lib.sm_cbca_double_config(ctx, 1, *param.cbca_double_args())
+            _capi.check(self._lib, ctx, st, "sm_cbca_double_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -308,6 +324,11 @@ class StereoBatch:
         # likewise "BF"'s window (sm_bf_config) and "GFNL"'s threshold (sm_gfnl_config)
         bf = [overrides.pop(k, d) for k, d in zip(("bf_ksize_v", "bf_ksize_u"), _capi.BF_DEFAULTS)]
         gfnl_thresh = overrides.pop("gfnl_var_thresh", _capi.GFNL_VAR_THRESH)
+        # CBCA's double window (sm_cbca_double_config): cbca_double_win switches it on, cbca_double_args are
+        # window 1's arm settings and the arm-length threshold (DistributedBatchRunner's compute function hands
+        # both through with its other overrides)
+        dw_on = bool(overrides.pop("cbca_double_win", False))
+        dw_args = tuple(overrides.pop("cbca_double_args", _capi.CBCA_DW_DEFAULTS))
         p = _capi.default_params(max_disp, rows, cols, **overrides)
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
@@ -321,6 +342,8 @@ class StereoBatch:
             self.bf_config(*bf)
         if gfnl_thresh != _capi.GFNL_VAR_THRESH:
             self.gfnl_config(gfnl_thresh)
+        if dw_on:
+            self.cbca_double_config(True, *dw_args)
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -445,6 +468,21 @@ class StereoBatch:
         """sm_gfnl_config: "GFNL"'s variance threshold (any finite value), from the next run on."""
         st = self._lib.sm_gfnl_config(self._ctx, float(var_thresh))
         _capi.check(self._lib, self._ctx, st, "gfnl_config")
+
+    def cbca_double_config(self, enable: bool = True, arm_l2: int = 23, arm_l_out2: int = 23, arm_c_thresh2: int = 30,
+                           arm_c_thresh_out2: int = 0, arm_len_thres: float = 5.0):
+        """sm_cbca_double_config: CBCA()'s double-window branch (two aggregations, fused per pixel by the
+        left image's window-0 arm lengths), from the next run on."""
+        st = self._lib.sm_cbca_double_config(self._ctx, int(bool(enable)), int(arm_l2), int(arm_l_out2),
+                                             int(arm_c_thresh2), int(arm_c_thresh_out2), float(arm_len_thres))
+        _capi.check(self._lib, self._ctx, st, "cbca_double_config")
+
+    def get_cbca_dw_mask(self) -> np.ndarray:
+        """sm_get_cbca_dw_mask: the first pair's arm_Mask [H][W] of the last run with the double window on."""
+        out = np.empty(self.shape[:2], np.uint8)
+        st = self._lib.sm_get_cbca_dw_mask(self._ctx, _capi.ptr(out))
+        _capi.check(self._lib, self._ctx, st, "get_cbca_dw_mask")
+        return out
 
     def vmtop_config(self, enable: bool = True, method: int = 0, num: int = 2, thres: float = 1.09, ts: int = 10,
                      has_cir2: bool = True, cir3_color_limit: bool = False):

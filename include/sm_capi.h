@@ -32,6 +32,12 @@
  *   sm_cbca_double_config <- Parameters::cbca_double_win, cbca_crossL[1] ..  stereoMatching.h:144, 263-275
  *                         (CBCA cpp:4333-4360, combine2Vm_4 cpp:4273-4331)
  *   sm_get_cbca_dw_mask <- member arm_Mask as combine2Vm_4 leaves it (cpp:4303-4318)
+ *   sm_refine_ext_config <- static switches Do_calPKR, Do_bgIpol, Do_subpixelEnhancement (h:73-81),
+ *                         calPKR's ratio_PKR (cpp:4093), Parameters::DISP_PKR (h:218), bgIplDepth (h:311)
+ *                         (calPKR + signDp_UsingPKR cpp:4087-4140, BGIpol cpp:7323-7338 +
+ *                          backgroundInterpolateCore cpp:7011-7043, subpixelEnhancement cpp:6138-6167)
+ *   sm_get_pkr_mask    <- member PKR_Err_Mask as calPKR leaves it (cpp:1380)
+ *   sm_get_subpixel / sm_download_subpixel <- refine()'s local SE after medianBlur(SE, SE, 3) (cpp:1484-1490)
  *   sm_get_volume / sm_set_volume <- public member vm[view]       stereoMatching.h:2720
  *   sm_get_arms        <- public member HVL[view]                    stereoMatching.h:2717
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
@@ -389,6 +395,43 @@ SM_API sm_status sm_get_top_disp(sm_ctx* ctx, int32_t view, float* dst);
  * cpp:4406-4418, so the facades accept the field and pass nothing on.) */
 SM_API sm_status sm_cbca_double_config(sm_ctx* ctx, int32_t enable, int32_t arm_l2, int32_t arm_l_out2,
                                        int32_t arm_c_thresh2, int32_t arm_c_thresh_out2, float arm_len_thres);
+
+/* subpixelEnhancement's two forms: */
+typedef enum sm_se_mode {
+    SM_SE_REFERENCE = 0,     /* the reference's `disp -= diff` on a short (cpp:6161): fl((float)d - diff) converted back
+                              * to short, truncating toward zero, so SE holds integers (mostly d - 1 where diff > 0) */
+    SM_SE_FLOAT = 1,         /* fl((float)d - diff) kept as a float: the sub-pixel disparity */
+} sm_se_mode;
+
+/* Three more stages of refine() (cpp:1347-1510), behind `static const bool` switches in the reference (h:73-81).
+ * refine()'s order is LR check -> PKR -> region votes -> properIpol -> BGIpol -> SE -> last median.
+ *   do_pkr       calPKR (cpp:4087-4126): c0, c1 = the smallest and second smallest (duplicates count) of a pixel's
+ *                num_disparities costs in vm[0] as dispOptimize left it; PKR_Err_Mask = 1 where
+ *                (c1 - c0) / c1 < pkr_ratio in float (ratio_PKR = 0.1f; 0 / 0 compares false); signDp_UsingPKR
+ *                (cpp:4128-4140) then sets DP[0] = disp_pkr (DISP_PKR = -64) where the mask is set and DP[0] >= 0.
+ *   do_bg_ipol   BGIpol (cpp:7323-7338): in raster order and IN PLACE every hole (DP[0] < 0) searches its row right,
+ *                then left, up to bg_ipl_depth (bgIplDepth = 1000) steps each for the first value >= 0 and takes the
+ *                only one found or the smaller of the two.  bg_ipl_depth = 0 fills nothing.
+ *   do_subpixel  subpixelEnhancement (cpp:6138-6167) on DP[0] and vm[0], then medianBlur(SE, SE, 3): a float map
+ *                per pair (se_mode: sm_se_mode), which the reference computes and drops; DP[0] is not changed.
+ * Not sm_params fields (the struct keeps its size): all off by default, takes effect from the next
+ * sm_disp_optimize / sm_refine / sm_run.  With do_pkr or do_subpixel and "sgm", SGM writes its path sum into
+ * vm[0] (as with keep_final_volume) for the stages to read; "" leaves the volume after SolveAll.  The maps are the
+ * same for every schedule.  The mask and the float maps are allocated on the first enabling call (batch_capacity
+ * pairs).  SM_EINVAL, with the argument named in sm_last_error, on a context without do_refine, for a pkr_ratio
+ * that is not finite, disp_pkr outside [-32768, -1], bg_ipl_depth outside [0, 32767], se_mode outside {0, 1},
+ * do_pkr with num_disparities < 2 (the reference's second search writes slot -1), and do_pkr or do_subpixel with
+ * optimization "so" (the reference's so rewrites vm in place, cpp:6299; this back end keeps a trace instead);
+ * the arguments are checked without a device.  Not built: Do_WM (reads a mask the shipped LR check never
+ * writes), Do_discontinuityAdjust and Do_cbbi (need an OpenCV the reference does not pin). */
+SM_API sm_status sm_refine_ext_config(sm_ctx* ctx, int32_t do_pkr, float pkr_ratio, int32_t disp_pkr, int32_t do_bg_ipol,
+                                      int32_t bg_ipl_depth, int32_t do_subpixel, int32_t se_mode);
+/* Pair 0's PKR_Err_Mask / float map SE of the last sm_refine / sm_run with the stage on: rows x cols bytes /
+ * floats.  SM_ESTATE before that. */
+SM_API sm_status sm_get_pkr_mask(sm_ctx* ctx, uint8_t* dst);
+SM_API sm_status sm_get_subpixel(sm_ctx* ctx, float* dst);
+/* The float maps of the first n pairs, [n][H][W], to a host or device pointer (synchronous). */
+SM_API sm_status sm_download_subpixel(sm_ctx* ctx, int32_t n, float* dst);
 
 /* Diagnostics used by the parity tests. */
 /* CBCA's double window: pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where

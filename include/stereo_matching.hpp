@@ -332,6 +332,16 @@ class StereoMatching {
     inline static bool Do_refine = false;          // h:70
     static constexpr bool Do_LRConsis = true;      // h:72
     inline static bool Do_regionVote = true;       // h:75
+    // three more of refine()'s stages (h:73-81; sm_refine_ext_config), off in the shipped build: the peak-ratio
+    // check (calPKR + signDp_UsingPKR), the background fill (BGIpol) and the sub-pixel map (subpixelEnhancement +
+    // its float median), which refine() leaves in SE.  Set before the object is constructed.
+    inline static bool Do_calPKR = false;
+    inline static bool Do_bgIpol = false;
+    inline static bool Do_subpixelEnhancement = false;
+    // SE's form: false reproduces the reference's `disp -= diff` on a short (cpp:6161: the float difference
+    // converted back, truncating toward zero), true keeps the float
+    inline static bool SE_FLOAT = false;
+    inline static float pkr_ratio = 0.1f;          // calPKR's local ratio_PKR (cpp:4093)
     inline static bool Do_properIpol = true;       // h:76
     inline static bool Do_lastMedianBlur = true;   // h:80
     // `#define MY_GUIDE` (h:38, commented out in the shipped build) as a switch: false = GF runs
@@ -380,6 +390,8 @@ class StereoMatching {
         int errorThreshold = 1;               // h:225
         float LRmaxDiff = 0;                  // h:212
         int DISP_OCC = -2 * 16;               // h:216
+        int DISP_PKR = -4 * 16;               // h:218
+        int bgIplDepth = 1000;                // h:311
         int region_vote_nums = 2;             // h:306
         // Parameters(maxDisp, h, w, lamCen, lamG, M, lamc, ts, errCsvName, disSc) — main_.cpp:138
         Parameters(int maxDisp, int h, int w, int lamCen_ = 13, int lamG_ = 1, int M = 2, int lamc = 109,
@@ -427,6 +439,14 @@ class StereoMatching {
     void refine() {  // cpp:1138-1511; needs Do_refine at construction
         DP[0].create(h_, w_, CV_16S);
         check(sm_refine(ctx_, DP[0].ptr<int16_t>()), "refine");
+        if (pkr_on_) {
+            PKR_Err_Mask.create(h_, w_, CV_8U);
+            check(sm_get_pkr_mask(ctx_, PKR_Err_Mask.ptr<uint8_t>()), "PKR_Err_Mask");
+        }
+        if (se_on_) {
+            SE.create(h_, w_, CV_32F);
+            check(sm_get_subpixel(ctx_, SE.ptr<float>()), "SE");
+        }
     }
     void pipeline() {  // cpp:1950-1981 (no SolveAll)
         costCalculate();
@@ -480,6 +500,8 @@ class StereoMatching {
 
     Mat DP[2];        // int16 H x W disparity, -1 = invalid (h:2724)
     Mat DT;           // ground truth (cpp:2072)
+    Mat SE;           // float H x W: refine()'s local SE after its median (cpp:1484-1490), with Do_subpixelEnhancement
+    Mat PKR_Err_Mask; // uint8 H x W: calPKR's mask (cpp:1380), with Do_calPKR
     Mat I_mask[3];    // nonocc, all, disc (cpp:2073-2075)
     Parameters param_;
     int h_, w_, d_;
@@ -487,6 +509,7 @@ class StereoMatching {
 
    private:
     bool refine_on_ = false, csv_open_ = false;
+    bool pkr_on_ = false, se_on_ = false;
     std::ostringstream csv_;
     std::vector<std::string> times_;
 
@@ -573,6 +596,13 @@ class StereoMatching {
             check(sm_cbca_double_config(ctx_, 1, param.cbca_crossL[1] / sc, param.cbca_crossL_out[1] / sc, param.cbca_cTresh[1],
                                         param.cbca_cTresh_out[1], 5.0f),
                   "sm_cbca_double_config");
+        if (Do_refine && (Do_calPKR || Do_bgIpol || Do_subpixelEnhancement)) {
+            check(sm_refine_ext_config(ctx_, Do_calPKR ? 1 : 0, pkr_ratio, param.DISP_PKR, Do_bgIpol ? 1 : 0, param.bgIplDepth,
+                                       Do_subpixelEnhancement ? 1 : 0, SE_FLOAT ? SM_SE_FLOAT : SM_SE_REFERENCE),
+                  "sm_refine_ext_config");
+            pkr_on_ = Do_calPKR;
+            se_on_ = Do_subpixelEnhancement;
+        }
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }
     void check(sm_status s, const char* what) {

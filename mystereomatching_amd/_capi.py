@@ -23,6 +23,9 @@ AWS_DEFAULTS = (17, 17, 5.0)   # radius_v, radius_u, gamma_c (sm_aws_config)
 BF_DEFAULTS = (12, 12)         # ksize_v, ksize_u (sm_bf_config)
 GFNL_VAR_THRESH = 400.0        # sm_gfnl_config
 CBCA_DW_DEFAULTS = (23, 23, 30, 0, 5.0)   # arm_l2, arm_l_out2, arm_c_thresh2, arm_c_thresh_out2, arm_len_thres
+SE_REFERENCE, SE_FLOAT = 0, 1
+# sm_refine_ext_config's values when a stage is on: pkr_ratio, disp_pkr, bg_ipl_depth, se_mode
+REFINE_EXT_DEFAULTS = (0.1, -64, 1000, SE_REFERENCE)
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -112,6 +115,10 @@ SIGNATURES = [
     ("sm_get_top_disp", C.c_int, [_P, C.c_int32, _P]),
     ("sm_cbca_double_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     ("sm_get_cbca_dw_mask", C.c_int, [_P, _P]),
+    ("sm_refine_ext_config", C.c_int, [_P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("sm_get_pkr_mask", C.c_int, [_P, _P]),
+    ("sm_get_subpixel", C.c_int, [_P, _P]),
+    ("sm_download_subpixel", C.c_int, [_P, C.c_int32, _P]),
 ]
 
 _lib = None

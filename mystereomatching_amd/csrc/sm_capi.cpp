@@ -121,6 +121,17 @@ struct sm_ctx {
     float* vm2 = nullptr;          // [cap][npix][D] + the volumes' tail pad
     uint8_t* dw_mask = nullptr;    // [cap][npix]
     bool dw_ran = false;           // the mask holds the last sm_cost_calculate / sm_run's choice
+    // refine()'s Do_calPKR, Do_bgIpol and Do_subpixelEnhancement stages (sm_refine_ext_config)
+    bool rx_pkr = false, rx_bg = false, rx_se = false;
+    float rx_ratio = 0.1f;         // ratio_PKR (cpp:4093)
+    int rx_disp_pkr = -4 * 16;     // DISP_PKR (h:218)
+    int rx_depth = 1000;           // bgIplDepth (h:311)
+    int rx_mode = SM_SE_REFERENCE;
+    uint8_t* pkr_mask = nullptr;   // [cap][npix] PKR_Err_Mask
+    float* se = nullptr;           // [cap][npix] SE after its median
+    float* se_tmp = nullptr;       // [cap][npix] SE before it (the median filters a copy)
+    bool rx_pkr_ran = false, rx_se_ran = false;   // the last refine filled the mask / the float maps
+    bool rx_vol_ok = true;         // no volume-reading stage was switched on since dispOptimize last ran
     // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -318,6 +329,8 @@ int cbca_lag2(const sm_ctx* c) { return c->dw_l_out > c->p.arm_min_l ? c->dw_l_o
 // cbca_core's iteration count: the double-window branch passes a literal 2 (cpp:4344, 4347) and never
 // reads cbca_iterations
 int cbca_iters(const sm_ctx* c) { return c->dw_on ? 2 : c->p.cbca_iterations; }
+// refine()'s calPKR / subpixelEnhancement are on: they read vm[0] after dispOptimize
+bool refine_reads_volume(const sm_ctx* c) { return c->p.do_refine && (c->rx_pkr || c->rx_se); }
 
 // combine2Vm_4's predicate on the nine-term sum s of integer arm maxima is boxFilter's (float)(s * (1.0 / 9))
 // (double sums, one rounding) < thres.  The product and its rounding are non-decreasing in s, so for every
@@ -523,7 +536,7 @@ void free_all(sm_ctx* c) {
                     c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w,
                     c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3],
                     c->bf_rs, c->gfnl_res, c->gfnl_mask, c->vt_tab, c->vt_cnt, c->vt_tcnt,
-                    c->arms2_alloc, c->vm2, c->dw_mask};
+                    c->arms2_alloc, c->vm2, c->dw_mask, c->pkr_mask, c->se, c->se_tmp};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -1285,7 +1298,8 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
     // Do_vmTop replaces gen_dispFromVm after "sgm" and "" (cpp:1108-1128); "so" never reaches it.  SGM then
     // writes its path sum into vm[view] (the keep_final_volume path) for the selection to read
     const bool vmtop = c->vt_on && p.optimization != SM_OPT_SO;
-    const int keep_final = p.keep_final_volume || vmtop;
+    // refine()'s calPKR and subpixelEnhancement read vm[0] as dispOptimize left it: the path sum (cpp:1380, 6152)
+    const int keep_final = p.keep_final_volume || vmtop || (view == 0 && refine_reads_volume(c));
     if (p.optimization == SM_OPT_SGM) {
         static const int RV[8] = {+1, -1, 0, 0, +1, +1, -1, -1};  // cpp:6207
         static const int RU[8] = {0, 0, +1, -1, -1, +1, +1, -1};  // cpp:6208
@@ -1413,6 +1427,22 @@ sm_status run_refine(sm_ctx* c, int n, const Bufs& B) {
     sm_status s = timed(c, "refine_lr_check", 3 * map,
                         [&] { sm::launch_lr_check(B.disp, B.disp1, n, H, W, p.lr_max_diff, c->st); });
     if (s) return s;
+    const size_t off = (size_t)(B.disp - c->disp);   // the group's first pixel
+    const double np = (double)n * c->npix;
+    if (c->rx_pkr) {   // calPKR + signDp_UsingPKR (cpp:1378-1383) on vm[0] as dispOptimize left it
+        sm::PkrArgs a{};
+        a.vm = B.vm0;
+        a.mask = c->pkr_mask + off;
+        a.disp = B.disp;
+        a.H = H;
+        a.W = W;
+        a.D = p.num_disparities;
+        a.n = n;
+        a.ratio = c->rx_ratio;
+        a.disp_pkr = c->rx_disp_pkr;
+        if ((s = timed(c, "refine_pkr", (double)n * c->nvol * 4.0 + np * 5, [&] { sm::launch_pkr(a, c->st); }))) return s;
+        c->rx_pkr_ran = true;
+    }
     int16_t* cur = B.disp;
     int16_t* nxt = B.disp_tmp;
     const uint32_t* arms = (const uint32_t*)B.arms;
@@ -1430,6 +1460,29 @@ sm_status run_refine(sm_ctx* c, int n, const Bufs& B) {
                 return s;
             std::swap(cur, nxt);
         }
+    if (c->rx_bg && c->rx_depth > 0) {   // BGIpol (cpp:1454-1465); a depth of 0 searches nothing
+        sm::BgArgs a{};
+        a.src = cur;
+        a.r = nxt;
+        a.H = H;
+        a.W = W;
+        a.n = n;
+        a.depth = c->rx_depth;
+        // k_bg_r reads the map and writes r; k_bg_scan reads both and writes the map
+        if ((s = timed(c, "refine_bg_ipol", 4 * map, [&] { sm::launch_bg_ipol(a, c->st); }))) return s;
+        std::swap(cur, nxt);
+    }
+    if (c->rx_se) {   // subpixelEnhancement + medianBlur(SE, SE, 3) (cpp:1482-1495); DP[0] stays
+        float* raw = c->se_tmp + off;
+        float* out = c->se + off;
+        const int keep = c->rx_mode == SM_SE_FLOAT;
+        if ((s = timed(c, "refine_subpixel", np * (2 + 12 + 4), [&] {
+                 sm::launch_subpixel(cur, B.vm0, raw, n, H, W, p.num_disparities, keep, c->st);
+             })))
+            return s;
+        if ((s = timed(c, "refine_median3_f32", np * 8, [&] { sm::launch_median3_f32(raw, out, n, H, W, c->st); }))) return s;
+        c->rx_se_ran = true;
+    }
     if (p.do_last_median_blur) {
         if ((s = timed(c, "refine_median3", 2 * map, [&] { sm::launch_median3(cur, nxt, n, H, W, c->st); }))) return s;
         std::swap(cur, nxt);
@@ -1960,6 +2013,7 @@ sm_status sm_disp_optimize(sm_ctx* c, int16_t* disp_out) {
     for (int v = 0; v < opt_views(c->p); v++)   // num (cpp:1054, 1093, 1110)
         if ((s = run_optimize(c, c->n_loaded, v, at(c, 0)))) return s;
     c->stage = 4;
+    c->rx_vol_ok = true;
     if (disp_out) return sm_download_disp(c, 1, disp_out);
     return SM_OK;
 }
@@ -1969,6 +2023,8 @@ sm_status sm_refine(sm_ctx* c, int16_t* disp_out) {
     if (s) return s;
     if (!c->p.do_refine) return fail(c, SM_ESTATE, "sm_refine needs do_refine = 1 at sm_create (DP[1] is not computed otherwise)");
     if (c->stage != 4) return fail(c, SM_ESTATE, "sm_refine must follow sm_disp_optimize");
+    if (refine_reads_volume(c) && c->p.optimization == SM_OPT_SGM && !c->p.keep_final_volume && !c->vt_on && !c->rx_vol_ok)
+        return fail(c, SM_ESTATE, "sm_refine: do_pkr / do_subpixel were switched on after sm_disp_optimize (SGM kept no path sum)");
     if ((s = wait_copy(c))) return s;
     if ((s = run_refine(c, c->n_loaded, at(c, 0)))) return s;
     c->stage = 5;
@@ -2009,7 +2065,8 @@ sm_status sm_get_volume(sm_ctx* c, int32_t view, float* dst) {
     if (c->stage < 2) return fail(c, SM_ESTATE, "no volume yet");
     float* src = view == 0 ? c->vm0 : (view == 1 ? c->vm1 : nullptr);
     if (!src) return fail(c, SM_EINVAL, view == 1 ? "right view not computed (compute_right_view = 0)" : "bad view");
-    if (c->stage >= 4 && !c->p.keep_final_volume && !c->vt_on && c->p.optimization == SM_OPT_SGM)
+    if (c->stage >= 4 && !c->p.keep_final_volume && !c->vt_on && !(view == 0 && refine_reads_volume(c) && c->rx_vol_ok) &&
+        c->p.optimization == SM_OPT_SGM)
         return fail(c, SM_ESTATE, "vm[view] after SGM is only kept with keep_final_volume = 1");
     HIP_TRY(c, hipMemcpyAsync(dst, src, c->nvol * 4, hipMemcpyDeviceToHost, c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
@@ -2229,6 +2286,7 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     }
     if (s_out) return s_out;
     c->stage = c->p.do_refine ? 5 : 4;
+    c->rx_vol_ok = true;
     if (disp_out) return sm_download_disp(c, n, disp_out);
     return SM_OK;
 }
@@ -2731,6 +2789,73 @@ sm_status sm_get_cbca_dw_mask(sm_ctx* c, uint8_t* dst) {
     HIP_TRY(c, hipStreamSynchronize(c->st));
     return SM_OK;
 }
+
+sm_status sm_refine_ext_config(sm_ctx* c, int32_t do_pkr, float pkr_ratio, int32_t disp_pkr, int32_t do_bg_ipol,
+                               int32_t bg_ipl_depth, int32_t do_subpixel, int32_t se_mode) {
+    if (!c) return SM_EINVAL;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (!c->p.do_refine) return fail(c, SM_EINVAL, "sm_refine_ext_config: the context has do_refine = 0 (refine() never runs)");
+    if (!std::isfinite(pkr_ratio)) return fail(c, SM_EINVAL, "pkr_ratio must be finite (ratio_PKR)");
+    if (disp_pkr < -32768 || disp_pkr > -1) return fail(c, SM_EINVAL, "disp_pkr must be in [-32768, -1] (DISP_PKR)");
+    if (bg_ipl_depth < 0 || bg_ipl_depth > 32767) return fail(c, SM_EINVAL, "bg_ipl_depth must be in [0, 32767] (bgIplDepth)");
+    if (se_mode != SM_SE_REFERENCE && se_mode != SM_SE_FLOAT)
+        return fail(c, SM_EINVAL, "se_mode must be SM_SE_REFERENCE (0) or SM_SE_FLOAT (1)");
+    if (do_pkr && c->p.num_disparities < 2)
+        return fail(c, SM_EINVAL, "do_pkr needs num_disparities >= 2 (calPKR's second search is undefined with one cost)");
+    if ((do_pkr || do_subpixel) && c->p.optimization == SM_OPT_SO)
+        return fail(c, SM_EINVAL, do_pkr ? "do_pkr: not with optimization so (the reference's so rewrites vm[0] in place)"
+                                         : "do_subpixel: not with optimization so (the reference's so rewrites vm[0] in place)");
+    if (c->st) {   // a live context
+        if ((do_pkr || do_subpixel) && !sm::refine_ext_shape_ok(c->p.rows, c->p.cols, c->cap))
+            return fail(c, SM_EINVAL, "sm_refine_ext_config: rows * cols * batch_capacity too large");
+        sm_status s = check(c);
+        if (s) return s;
+        const size_t cap = (size_t)c->cap;
+        if (do_pkr && !c->pkr_mask && (s = dalloc(c, &c->pkr_mask, cap * c->npix))) return s;
+        if (do_subpixel && !c->se) {
+            if ((s = dalloc(c, &c->se, cap * c->npix))) return s;
+            if (!c->se_tmp && (s = dalloc(c, &c->se_tmp, cap * c->npix))) return s;
+        }
+    }
+    const bool live = c->st != nullptr;
+    const bool reads = live && (do_pkr || do_subpixel);
+    // SGM keeps its path sum in vm[0] only while a stage reads it: one switched on after dispOptimize ran needs a
+    // new sm_disp_optimize
+    if (reads && !refine_reads_volume(c)) c->rx_vol_ok = false;
+    c->rx_pkr = live && do_pkr;
+    c->rx_bg = live && do_bg_ipol;
+    c->rx_se = live && do_subpixel;
+    c->rx_ratio = pkr_ratio;
+    c->rx_disp_pkr = disp_pkr;
+    c->rx_depth = bg_ipl_depth;
+    c->rx_mode = se_mode;
+    c->rx_pkr_ran = c->rx_se_ran = false;
+    return SM_OK;
+}
+
+sm_status sm_get_pkr_mask(sm_ctx* c, uint8_t* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst) return fail(c, SM_EINVAL, "null dst");
+    if (!c->rx_pkr || !c->rx_pkr_ran || c->stage < 5)
+        return fail(c, SM_ESTATE, "no mask yet (sm_refine_ext_config with do_pkr, then sm_refine / sm_run)");
+    HIP_TRY(c, hipMemcpyAsync(dst, c->pkr_mask, c->npix, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
+
+sm_status sm_download_subpixel(sm_ctx* c, int32_t n, float* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst || n < 1 || n > c->cap) return fail(c, SM_EINVAL, "bad arguments");
+    if (!c->rx_se || !c->rx_se_ran || c->stage < 5)
+        return fail(c, SM_ESTATE, "no sub-pixel map yet (sm_refine_ext_config with do_subpixel, then sm_refine / sm_run)");
+    HIP_TRY(c, hipMemcpyAsync(dst, c->se, (size_t)n * c->npix * sizeof(float), hipMemcpyDefault, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
+
+sm_status sm_get_subpixel(sm_ctx* c, float* dst) { return sm_download_subpixel(c, 1, dst); }
 
 void sm_bgr2lab_host(const uint8_t* bgr, size_t npix, uint8_t* lab) {
     if (!bgr || !lab) return;

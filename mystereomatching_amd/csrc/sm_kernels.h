@@ -358,4 +358,26 @@ struct DwArgs {
 void launch_dw_mask(const DwArgs& a, int n, hipStream_t st);     // H, W >= 2
 void launch_dw_select(const DwArgs& a, int n, hipStream_t st);
 
+// refine()'s Do_calPKR, Do_bgIpol and Do_subpixelEnhancement stages (sm_refine_ext.hip); pair-relative bases
+struct PkrArgs {
+    const float* vm;            // [n][H][W][D] vm[0] as dispOptimize left it
+    uint8_t* mask;              // [n][H][W] PKR_Err_Mask
+    int16_t* disp;              // [n][H][W] DP[0]: marked pixels >= 0 become disp_pkr
+    int H, W, D, n;
+    float ratio;                // ratio_PKR
+    int disp_pkr;               // DISP_PKR
+};
+struct BgArgs {
+    const int16_t* src;         // [n][H][W] the map before the stage
+    int16_t* r;                 // [n][H][W] the right candidates, then the filled map
+    int H, W, n;
+    int depth;                  // bgIplDepth >= 1
+};
+bool refine_ext_shape_ok(int H, int W, int n);
+void launch_pkr(const PkrArgs& a, hipStream_t st);                 // D >= 2
+void launch_bg_ipol(const BgArgs& a, hipStream_t st);              // k_bg_r, then k_bg_scan
+void launch_subpixel(const int16_t* dp, const float* vm, float* se, int n, int H, int W, int D, int keep_float,
+                     hipStream_t st);
+void launch_median3_f32(const float* src, float* dst, int n, int H, int W, hipStream_t st);
+
 }  // namespace sm

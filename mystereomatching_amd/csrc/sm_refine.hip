@@ -240,3 +240,5 @@ void launch_median3(const int16_t* src, int16_t* dst, int n, int H, int W, hipSt
 }
 
 }  // namespace sm
+
+#include "sm_refine_ext.hip"   // refine()'s peak-ratio check, background fill and sub-pixel map

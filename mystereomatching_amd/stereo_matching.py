@@ -52,6 +52,15 @@ class StereoMatching:
     Do_regionVote = True
     Do_properIpol = True
     Do_lastMedianBlur = True
+    # three more of refine()'s stages (h:73-81; sm_refine_ext_config), off in the shipped build: the peak-ratio
+    # check (calPKR + signDp_UsingPKR), the background fill (BGIpol) and the sub-pixel map (subpixelEnhancement +
+    # its float median), which refine() leaves in self.SE.  SE_FLOAT keeps the float difference; False reproduces
+    # the reference's `disp -= diff` on a short (cpp:6161)
+    Do_calPKR = False
+    Do_bgIpol = False
+    Do_subpixelEnhancement = False
+    SE_FLOAT = False
+    PKR_RATIO = _capi.REFINE_EXT_DEFAULTS[0]   # calPKR's local ratio_PKR (cpp:4093)
 
     class Parameters:
         """StereoMatching::Parameters (h:85-351): the fields the hot path reads."""
@@ -97,6 +106,8 @@ class StereoMatching:
             self.rows, self.cols = h, w
             self.LRmaxDiff = 0.0                       # h:212
             self.DISP_OCC = -2 * 16                    # h:216
+            self.DISP_PKR = -4 * 16                    # h:218
+            self.bgIplDepth = 1000                     # h:311
             self.region_vote_nums = 2                  # h:306
             self.rv_ratio, self.rv_s = 0.4, 20         # refine(): rv_ratio[] / rv_s[] (cpp:1400-1401)
 
@@ -193,6 +204,14 @@ class StereoMatching:
         if param.cbca_double_win and self.aggregation == "CBCA":
             st = self._lib.sm_cbca_double_config(ctx, 1, *param.cbca_double_args())
             _capi.check(self._lib, ctx, st, "sm_cbca_double_config")
+        self.SE: Optional[np.ndarray] = None            # refine()'s float map (Do_subpixelEnhancement)
+        self.PKR_Err_Mask: Optional[np.ndarray] = None  # calPKR's mask (Do_calPKR)
+        self._refine_ext = (bool(self.Do_calPKR), bool(self.Do_bgIpol), bool(self.Do_subpixelEnhancement))
+        if self._refine_on and any(self._refine_ext):
+            st = self._lib.sm_refine_ext_config(ctx, int(self.Do_calPKR), float(self.PKR_RATIO), int(param.DISP_PKR),
+                                                int(self.Do_bgIpol), int(param.bgIplDepth), int(self.Do_subpixelEnhancement),
+                                                _capi.SE_FLOAT if self.SE_FLOAT else _capi.SE_REFERENCE)
+            _capi.check(self._lib, ctx, st, "sm_refine_ext_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -221,11 +240,18 @@ class StereoMatching:
         return dp
 
     def refine(self):
-        """refine() (cpp:1138-1511): LR check against DP[1], region votes, proper interpolation,
-        3x3 median -> DP[0].  Needs Do_refine = True when the object was constructed."""
+        """refine() (cpp:1138-1511): LR check against DP[1], [peak-ratio check,] region votes, proper
+        interpolation, [background fill, sub-pixel map -> SE,] 3x3 median -> DP[0].  Needs Do_refine = True when
+        the object was constructed."""
         dp = np.empty((self.h_, self.w_), np.int16)
         _capi.check(self._lib, self._ctx, self._lib.sm_refine(self._ctx, _capi.ptr(dp)), "refine")
         self.DP[0] = dp
+        if self._refine_ext[0]:
+            self.PKR_Err_Mask = np.empty((self.h_, self.w_), np.uint8)
+            _capi.check(self._lib, self._ctx, self._lib.sm_get_pkr_mask(self._ctx, _capi.ptr(self.PKR_Err_Mask)), "PKR_Err_Mask")
+        if self._refine_ext[2]:
+            self.SE = np.empty((self.h_, self.w_), np.float32)
+            _capi.check(self._lib, self._ctx, self._lib.sm_get_subpixel(self._ctx, _capi.ptr(self.SE)), "SE")
         return dp
 
     def pipeline(self):
@@ -329,6 +355,8 @@ class StereoBatch:
         # both through with its other overrides)
         dw_on = bool(overrides.pop("cbca_double_win", False))
         dw_args = tuple(overrides.pop("cbca_double_args", _capi.CBCA_DW_DEFAULTS))
+        # refine()'s extra stages (sm_refine_ext_config): refine_ext is a dict of refine_ext_config's arguments
+        refine_ext = overrides.pop("refine_ext", None)
         p = _capi.default_params(max_disp, rows, cols, **overrides)
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
@@ -344,6 +372,8 @@ class StereoBatch:
             self.gfnl_config(gfnl_thresh)
         if dw_on:
             self.cbca_double_config(True, *dw_args)
+        if refine_ext:
+            self.refine_ext_config(**dict(refine_ext))
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -482,6 +512,40 @@ class StereoBatch:
         out = np.empty(self.shape[:2], np.uint8)
         st = self._lib.sm_get_cbca_dw_mask(self._ctx, _capi.ptr(out))
         _capi.check(self._lib, self._ctx, st, "get_cbca_dw_mask")
+        return out
+
+    def refine_ext_config(self, do_pkr: bool = False, pkr_ratio: float = _capi.REFINE_EXT_DEFAULTS[0],
+                          disp_pkr: int = _capi.REFINE_EXT_DEFAULTS[1], do_bg_ipol: bool = False,
+                          bg_ipl_depth: int = _capi.REFINE_EXT_DEFAULTS[2], do_subpixel: bool = False,
+                          se_mode: int = _capi.REFINE_EXT_DEFAULTS[3]):
+        """sm_refine_ext_config: refine()'s peak-ratio check, background fill and sub-pixel map (all off by
+        default), from the next run on; needs do_refine = 1."""
+        st = self._lib.sm_refine_ext_config(self._ctx, int(bool(do_pkr)), float(pkr_ratio), int(disp_pkr),
+                                            int(bool(do_bg_ipol)), int(bg_ipl_depth), int(bool(do_subpixel)), int(se_mode))
+        _capi.check(self._lib, self._ctx, st, "refine_ext_config")
+
+    def get_pkr_mask(self) -> np.ndarray:
+        """sm_get_pkr_mask: the first pair's PKR_Err_Mask [H][W] of the last run with do_pkr on."""
+        out = np.empty(self.shape[:2], np.uint8)
+        _capi.check(self._lib, self._ctx, self._lib.sm_get_pkr_mask(self._ctx, _capi.ptr(out)), "get_pkr_mask")
+        return out
+
+    def download_subpixel(self, out=None):
+        """sm_download_subpixel: the n float maps SE [n][H][W] of the last run with do_subpixel on, into a new
+        numpy array or into `out` (a C-contiguous float32 numpy array, or a float32 torch tensor on the GPU)."""
+        need = self.n * self.shape[0] * self.shape[1]
+        if out is None:
+            out = np.empty((self.n, self.shape[0], self.shape[1]), np.float32)
+        if type(out).__module__.startswith("torch"):
+            import torch
+            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < need:
+                raise ValueError(f"download_subpixel: out must be a contiguous float32 tensor of at least {need} elements")
+            dst = C.c_void_p(out.data_ptr())
+        else:
+            if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags["C_CONTIGUOUS"] or out.size < need:
+                raise ValueError(f"download_subpixel: out must be a C-contiguous float32 array of at least {need} elements")
+            dst = _capi.ptr(out)
+        _capi.check(self._lib, self._ctx, self._lib.sm_download_subpixel(self._ctx, self.n, dst), "download_subpixel")
         return out
 
     def vmtop_config(self, enable: bool = True, method: int = 0, num: int = 2, thres: float = 1.09, ts: int = 10,

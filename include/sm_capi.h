@@ -32,6 +32,9 @@
  *   sm_cbca_double_config <- Parameters::cbca_double_win, cbca_crossL[1] ..  stereoMatching.h:144, 263-275
  *                         (CBCA cpp:4333-4360, combine2Vm_4 cpp:4273-4331)
  *   sm_get_cbca_dw_mask <- member arm_Mask as combine2Vm_4 leaves it (cpp:4303-4318)
+ *   sm_cbca_intersect_config <- Parameters::cbca_intersect                 stereoMatching.h:139, 262
+ *                         (cbca_core cpp:5585-5666, gen1DCumu cpp:3896-3926, cal1DCost h:1643-1715)
+ *   sm_get_cbca_area   <- cbca_core's local `area` after its last iteration (cpp:5606)
  *   sm_refine_ext_config <- static switches Do_calPKR, Do_bgIpol, Do_subpixelEnhancement (h:73-81),
  *                         calPKR's ratio_PKR (cpp:4093), Parameters::DISP_PKR (h:218), bgIplDepth (h:311)
  *                         (calPKR + signDp_UsingPKR cpp:4087-4140, BGIpol cpp:7323-7338 +
@@ -396,6 +399,23 @@ SM_API sm_status sm_get_top_disp(sm_ctx* ctx, int32_t view, float* dst);
 SM_API sm_status sm_cbca_double_config(sm_ctx* ctx, int32_t enable, int32_t arm_l2, int32_t arm_l_out2,
                                        int32_t arm_c_thresh2, int32_t arm_c_thresh_out2, float arm_len_thres);
 
+/* Cross-based aggregation without arm intersection (Parameters::cbca_intersect = false, h:139, 262; cbca_core
+ * cpp:5585-5666 with gen1DCumu cpp:3896-3926, cal1DCost h:1643-1715, genfinalVm_cbca cpp:3969-3992).  With
+ * intersect = 0 the support region of a pixel comes from the arms of the view's own image alone (HVL[view]: the
+ * left image's for vm[0], the right image's for vm[1]), is the same for every disparity, and has one int32 area
+ * per pixel: every iteration starts from area = ones, runs two 1-D passes (H then V for an even iteration, V then
+ * H for an odd one) -- a sequential f32 prefix sum along the axis, then per pixel S(x + head) - S(x - tail - 1), or
+ * S(x + head) alone where x - tail - 1 < 0, and the same in integers for the area -- and divides by (float)area.
+ * Default 1 (the intersecting form).  Not an sm_params field (the struct keeps its size); takes effect from the
+ * next sm_cost_calculate / sm_run.  With 0: the costs always come from the cost volume kernel (every cost
+ * method), fuse_cost_scan, fuse_norm_scan, sub_batch and num_streams change nothing in the maps,
+ * cbca_iterations 0 .. 64 is honoured, the double window sends both of its runs through this form, profile names
+ * end in "_ni"; sm_get_arms, refine() and the pyramid path work as before.  One more volume and the area planes
+ * are allocated on the first call with 0 (batch_capacity pairs); a context that has had intersection off runs no
+ * placement trials.  SM_EINVAL, with the argument named in sm_last_error, on a context whose aggregation is not
+ * SM_AGG_CBCA and for a value outside {0, 1}; both are checked without a device. */
+SM_API sm_status sm_cbca_intersect_config(sm_ctx* ctx, int32_t intersect);
+
 /* subpixelEnhancement's two forms: */
 typedef enum sm_se_mode {
     SM_SE_REFERENCE = 0,     /* the reference's `disp -= diff` on a short (cpp:6161): fl((float)d - diff) converted back
@@ -437,6 +457,9 @@ SM_API sm_status sm_download_subpixel(sm_ctx* ctx, int32_t n, float* dst);
 /* CBCA's double window: pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where
  * vm[view] holds the window-1 costs). */
 SM_API sm_status sm_get_cbca_dw_mask(sm_ctx* ctx, uint8_t* dst);
+/* CBCA without arm intersection: pair 0's per-pixel support area of view `view` after the last iteration of the
+ * last sm_cost_calculate / sm_run, rows x cols int32.  SM_ESTATE before that, or with intersection on. */
+SM_API sm_status sm_get_cbca_area(sm_ctx* ctx, int32_t view, int32_t* dst);
 /* "GFNL": pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where the variance
  * is below the threshold, i.e. where vm[0] is NL's value alone). */
 SM_API sm_status sm_get_gfnl_mask(sm_ctx* ctx, uint8_t* dst);

@@ -383,6 +383,9 @@ class StereoMatching {
         // CBCA()'s double-window branch (h:144, 275; cpp:4337-4357; sm_cbca_double_config): set before the object
         // is constructed.  Both aggregations then do two iterations whatever cbca_iterationNum says.
         bool cbca_double_win = false;
+        // h:139, 262; false: cross-based aggregation without arm intersection (sm_cbca_intersect_config): the view's
+        // own arms, one area per pixel.  Set before the object is constructed; only "CBCA" reads it.
+        bool cbca_intersect = true;
         // GF()'s double-window switch (h:145, 276): both arms of the reference's branch run guideFilter(0, vm)
         // (cpp:4406-4418), so the field is accepted and changes nothing
         bool GF_double_win = false;
@@ -596,6 +599,7 @@ class StereoMatching {
             check(sm_cbca_double_config(ctx_, 1, param.cbca_crossL[1] / sc, param.cbca_crossL_out[1] / sc, param.cbca_cTresh[1],
                                         param.cbca_cTresh_out[1], 5.0f),
                   "sm_cbca_double_config");
+        if (!param.cbca_intersect && aggregation == "CBCA") check(sm_cbca_intersect_config(ctx_, 0), "sm_cbca_intersect_config");
         if (Do_refine && (Do_calPKR || Do_bgIpol || Do_subpixelEnhancement)) {
             check(sm_refine_ext_config(ctx_, Do_calPKR ? 1 : 0, pkr_ratio, param.DISP_PKR, Do_bgIpol ? 1 : 0, param.bgIplDepth,
                                        Do_subpixelEnhancement ? 1 : 0, SE_FLOAT ? SM_SE_FLOAT : SM_SE_REFERENCE),

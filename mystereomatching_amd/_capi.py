@@ -115,6 +115,8 @@ SIGNATURES = [
     ("sm_get_top_disp", C.c_int, [_P, C.c_int32, _P]),
     ("sm_cbca_double_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     ("sm_get_cbca_dw_mask", C.c_int, [_P, _P]),
+    ("sm_cbca_intersect_config", C.c_int, [_P, C.c_int32]),
+    ("sm_get_cbca_area", C.c_int, [_P, C.c_int32, _P]),
     ("sm_refine_ext_config", C.c_int, [_P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("sm_get_pkr_mask", C.c_int, [_P, _P]),
     ("sm_get_subpixel", C.c_int, [_P, _P]),

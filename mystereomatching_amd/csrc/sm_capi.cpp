@@ -121,6 +121,13 @@ struct sm_ctx {
     float* vm2 = nullptr;          // [cap][npix][D] + the volumes' tail pad
     uint8_t* dw_mask = nullptr;    // [cap][npix]
     bool dw_ran = false;           // the mask holds the last sm_cost_calculate / sm_run's choice
+    // cbca_core without arm intersection (sm_cbca_intersect_config(ctx, 0); sm_cbca_ni.hip): the other volume of
+    // the passes' ping-pong (one serves both views and both windows: they run one after the other on the group's
+    // stream) and the per-pixel areas
+    bool ni_on = false;
+    float* ni_tmp = nullptr;       // [cap][npix][D]
+    int32_t* ni_area = nullptr;    // [cap][2 views][2 planes][npix]; an iteration leaves its areas in plane 0
+    bool ni_ran = false;           // plane 0 holds the areas of the last sm_cost_calculate / sm_run's last iteration
     // refine()'s Do_calPKR, Do_bgIpol and Do_subpixelEnhancement stages (sm_refine_ext_config)
     bool rx_pkr = false, rx_bg = false, rx_se = false;
     float rx_ratio = 0.1f;         // ratio_PKR (cpp:4093)
@@ -536,7 +543,7 @@ void free_all(sm_ctx* c) {
                     c->nl_offs, c->luts, c->nl_vc, c->nl_fl, c->fif_s, c->fif_w,
                     c->aws_tab, c->aws_lab, c->aws_raw, c->aws_band[0], c->aws_band[1], c->aws_band[2], c->aws_band[3],
                     c->bf_rs, c->gfnl_res, c->gfnl_mask, c->vt_tab, c->vt_cnt, c->vt_tcnt,
-                    c->arms2_alloc, c->vm2, c->dw_mask, c->pkr_mask, c->se, c->se_tmp};
+                    c->arms2_alloc, c->vm2, c->dw_mask, c->pkr_mask, c->se, c->se_tmp, c->ni_tmp, c->ni_area};
     for (void* q : ptrs)
         if (q) hipFree(q);
     if (c->nl_st) {
@@ -705,7 +712,8 @@ bool cost_scan_fused(const sm_ctx* c, int view) {
     const int cw = (census_len(p) + 31) / 32;
     // (the double window runs the sweep once per arm set: the longer lag decides)
     const int lag = c->dw_on ? std::max(cbca_lag(p), cbca_lag2(c)) : cbca_lag(p);
-    return c->fuse_cost_scan && p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0 && view < n_views(p) &&
+    // (without arm intersection the costs come from the cost volume: the fused scan is the intersecting sweep)
+    return c->fuse_cost_scan && !c->ni_on && p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0 && view < n_views(p) &&
            p.cost_method == SM_COST_CENSUS_GRAD && cw >= 3 && p.lam_g == 1.0f &&
            sm::cost_nosel_ok(p.grad_trunc, p.lam_g, (float)census_len(p)) &&
            sm::cbca_hsc_smem_bytes(lag, cw) <= 64 * 1024;
@@ -757,6 +765,55 @@ sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
                  [&] { sm::launch_cost(a, m, n, c->st); });
 }
 
+// cbca_core with cbca_intersect == false (cpp:5585-5666) on a view: the arms of the view's own image, one area per
+// pixel.  Each 1-D pass is a prefix kernel (in place) and a window kernel that writes the other volume of the
+// ping-pong (the view's volume -> ni_tmp -> the view's volume), so every iteration ends in the view's volume;
+// its second window kernel divides by the area and, in the last iteration of sm_run, applies SolveAll's weight
+// (scaling an element commutes with nothing else after the division).  The areas ping-pong between the two
+// planes the same way and end in plane 0.
+sm_status run_cbca_ni(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B, int win) {
+    const sm_params& p = c->p;
+    const int N = cbca_iters(c);
+    const size_t pair_off = (size_t)(B.vm0 - c->vm0);
+    float* vol = win ? c->vm2 + pair_off : (view == 0 ? B.vm0 : B.vm1);
+    float* tmp = c->ni_tmp + pair_off;
+    sm::NiArgs a{};
+    a.arms = (const uint32_t*)(win ? c->arms2 + (size_t)(B.arms - c->arms) : B.arms);
+    a.area = c->ni_area + pair_off / c->nvol * 4 * c->npix;
+    a.H = p.rows;
+    a.W = p.cols;
+    a.D = p.num_disparities;
+    a.view = view;
+    a.scale = w;
+    // algorithmic bytes: the prefix reads and writes the volume; the window reads every prefix position once
+    // from memory (it is the head of one pixel and the tail of another) and writes the other volume
+    const double bytes = (double)n * c->nvol * 8.0;
+    const std::string sfx = std::string(view == 0 ? "" : "_r") + (win ? "_dw" : "") + "_ni";
+    sm_status s;
+    for (int k = 0; k < N; k++) {
+        for (int pass = 0; pass < 2; pass++) {
+            a.horiz = (k % 2 == 0) == (pass == 0) ? 1 : 0;   // H then V for even k, V then H for odd k
+            a.src = pass == 0 ? vol : tmp;
+            a.dst = pass == 0 ? tmp : vol;
+            a.in_plane = pass;
+            a.first = pass == 0;
+            a.norm = pass == 1;
+            a.apply_scale = fuse_scale && pass == 1 && k + 1 == N ? 1 : 0;
+            const std::string dir = a.horiz ? "cbca_h_" : "cbca_v_";
+            if ((s = timed(c, (dir + "prefix" + sfx).c_str(), bytes, [&] { sm::launch_ni_prefix(a, n, c->st); }))) return s;
+            if ((s = timed(c, (dir + (a.norm ? "window_norm" : "window") + sfx).c_str(), bytes,
+                           [&] { sm::launch_ni_window(a, n, c->st); })))
+                return s;
+            if (!win && c->stagger_ev) {   // the next group may start (as after the intersecting form's first sweep)
+                HIP_TRY(c, hipEventRecord(c->stagger_ev, c->st));
+                c->stagger_ev = nullptr;
+            }
+        }
+    }
+    c->ni_ran = true;
+    return SM_OK;
+}
+
 // One cbca_core run on a view.  win 0: the view's volume with the window-0 arms (the only run without the
 // double window).  win 1: the double window's large-window run, on the second volume with window 1's arms,
 // lag and ring size; it records none of the group's events (the window-0 run that follows reads the same
@@ -768,6 +825,7 @@ sm_status run_cbca_core(sm_ctx* c, int n, int view, bool fuse_scale, float w, co
     const sm_params& p = c->p;
     const int N = cbca_iters(c);
     if (N <= 0) return SM_OK;
+    if (c->ni_on) return run_cbca_ni(c, n, view, fuse_scale, w, B, win);
     const size_t pair_off = (size_t)(B.vm0 - c->vm0);   // floats from the allocation base to the group's first pair
     sm::CbcaArgs a{};
     a.vm = win ? c->vm2 + pair_off : (view == 0 ? B.vm0 : B.vm1);
@@ -2786,6 +2844,45 @@ sm_status sm_get_cbca_dw_mask(sm_ctx* c, uint8_t* dst) {
     if (!c->dw_on || !c->dw_ran || c->stage < 2)
         return fail(c, SM_ESTATE, "no mask yet (sm_cbca_double_config, then sm_cost_calculate / sm_run)");
     HIP_TRY(c, hipMemcpyAsync(dst, c->dw_mask, c->npix, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
+
+sm_status sm_cbca_intersect_config(sm_ctx* c, int32_t intersect) {
+    if (!c) return SM_EINVAL;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (c->p.aggregation != SM_AGG_CBCA)
+        return fail(c, SM_EINVAL, "sm_cbca_intersect_config: the context's aggregation is not SM_AGG_CBCA");
+    if (intersect != 0 && intersect != 1) return fail(c, SM_EINVAL, "intersect must be 0 or 1 (cbca_intersect)");
+    const bool off = intersect == 0 && c->st != nullptr;
+    if (c->st) {   // a live context: nothing queued may still run under the old setting
+        sm_status s = check(c);
+        if (s) return s;
+        if (off && (!c->ni_tmp || !c->ni_area)) {
+            HIP_TRY(c, hipStreamSynchronize(c->st));
+            c->ni_on = false;   // (stays off if an allocation below fails)
+            const size_t cap = (size_t)c->cap;
+            if (!c->ni_tmp && (s = dalloc(c, &c->ni_tmp, cap * c->nvol))) return s;
+            if (!c->ni_area && (s = dalloc(c, &c->ni_area, cap * 4 * c->npix))) return s;
+        }
+        // placement trials time one volume set against another; the ping-pong volume is not part of a set, so a
+        // context that has had intersection off chooses no placement (the maps are the same either way)
+        if (off) c->place_trials = 0;
+    }
+    c->ni_on = off;
+    c->ni_ran = false;
+    return SM_OK;
+}
+
+sm_status sm_get_cbca_area(sm_ctx* c, int32_t view, int32_t* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst) return fail(c, SM_EINVAL, "null dst");
+    if (view < 0 || view >= n_views(c->p)) return fail(c, SM_EINVAL, "view must be 0, or 1 with do_refine");
+    if (!c->ni_on || !c->ni_ran || c->stage < 2)
+        return fail(c, SM_ESTATE, "no areas yet (sm_cbca_intersect_config(ctx, 0), then sm_cost_calculate / sm_run)");
+    HIP_TRY(c, hipMemcpyAsync(dst, c->ni_area + (size_t)view * 2 * c->npix, c->npix * sizeof(int32_t), hipMemcpyDeviceToHost,
+                              c->st));
     HIP_TRY(c, hipStreamSynchronize(c->st));
     return SM_OK;
 }

@@ -1905,6 +1905,8 @@ void launch_cbca(const CbcaArgs& a, bool horiz, int mode, int n, hipStream_t st)
 // translation unit: the host-side sanitizer build of the C ABI (tests/test_sanitizers.py) links a fixed list of
 // kernel objects, so a new launcher has to live in one of them.
 #include "sm_cbca_dw.hip"
+// ... and so is cbca_core without arm intersection (cbca_intersect == false: prefix and window kernels)
+#include "sm_cbca_ni.hip"
 
 #if SM_CB_NSV_TRACE
 // diagnostic builds only: [block][wave][phase] cycle sums of the last NsV2 launch (phase 7 = tiles)

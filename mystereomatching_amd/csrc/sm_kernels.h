@@ -358,6 +358,25 @@ struct DwArgs {
 void launch_dw_mask(const DwArgs& a, int n, hipStream_t st);     // H, W >= 2
 void launch_dw_select(const DwArgs& a, int n, hipStream_t st);
 
+// cbca_core without arm intersection (sm_cbca_ni.hip): one 1-D pass is launch_ni_prefix, then launch_ni_window
+struct NiArgs {
+    float* src;                 // the pass's input of the launch's first pair [n][H][W][D]: prefixed in place
+    float* dst;                 // the pass's output (the other volume of the ping-pong), same shape
+    const uint32_t* arms;       // the launch's first pair: [n][view][plane][H][W], plane 0 = L | R<<16, plane 1 = U | D<<16
+    int32_t* area;              // the launch's first pair: [n][view][2][H][W]; the pass reads plane in_plane
+                                // (prefixed in place) and writes the other one
+    int H, W, D;
+    int view;                   // 0: the left image's arms (vm[0]), 1: the right image's (vm[1])
+    int horiz;                  // 1: lines are rows, 0: columns
+    int in_plane;
+    int first;                  // 1: the first pass of an iteration: the area going in is ones(h, w), not read
+    int norm;                   // 1: the second pass: the window kernel divides by the area it computes
+    int apply_scale;            // with norm: SolveAll's weight on the quotient
+    float scale;
+};
+void launch_ni_prefix(const NiArgs& a, int n, hipStream_t st);
+void launch_ni_window(const NiArgs& a, int n, hipStream_t st);   // H <= 65535 (sm_params' limit for rows)
+
 // refine()'s Do_calPKR, Do_bgIpol and Do_subpixelEnhancement stages (sm_refine_ext.hip); pair-relative bases
 struct PkrArgs {
     const float* vm;            // [n][H][W][D] vm[0] as dispOptimize left it

@@ -76,7 +76,9 @@ class StereoMatching:
             self.grad_use2direc = True                 # h:246
             self.cbca_minArmL = 1                      # h:259
             self.cbca_iterationNum = 2                 # h:260
-            self.cbca_intersect = True                 # h:262
+            # h:262; False: the aggregation without arm intersection (sm_cbca_intersect_config), read when the
+            # object is constructed and only by "CBCA"
+            self.cbca_intersect = True
             self.cbca_crossL = [17, 23, 34]            # h:263-265
             self.cbca_crossL_out = [34, 23, 34]        # h:266-268
             self.cbca_cTresh = [20, 30, 30]            # h:269-271
@@ -204,6 +206,9 @@ class StereoMatching:
         if param.cbca_double_win and self.aggregation == "CBCA":
             st = self._lib.sm_cbca_double_config(ctx, 1, *param.cbca_double_args())
             _capi.check(self._lib, ctx, st, "sm_cbca_double_config")
+        if not param.cbca_intersect and self.aggregation == "CBCA":   # (only the CBCA functions read the field)
+            st = self._lib.sm_cbca_intersect_config(ctx, 0)
+            _capi.check(self._lib, ctx, st, "sm_cbca_intersect_config")
         self.SE: Optional[np.ndarray] = None            # refine()'s float map (Do_subpixelEnhancement)
         self.PKR_Err_Mask: Optional[np.ndarray] = None  # calPKR's mask (Do_calPKR)
         self._refine_ext = (bool(self.Do_calPKR), bool(self.Do_bgIpol), bool(self.Do_subpixelEnhancement))
@@ -355,6 +360,8 @@ class StereoBatch:
         # both through with its other overrides)
         dw_on = bool(overrides.pop("cbca_double_win", False))
         dw_args = tuple(overrides.pop("cbca_double_args", _capi.CBCA_DW_DEFAULTS))
+        # CBCA without arm intersection (sm_cbca_intersect_config): cbca_intersect=False switches to it
+        intersect = bool(overrides.pop("cbca_intersect", True))
         # refine()'s extra stages (sm_refine_ext_config): refine_ext is a dict of refine_ext_config's arguments
         refine_ext = overrides.pop("refine_ext", None)
         p = _capi.default_params(max_disp, rows, cols, **overrides)
@@ -372,6 +379,8 @@ class StereoBatch:
             self.gfnl_config(gfnl_thresh)
         if dw_on:
             self.cbca_double_config(True, *dw_args)
+        if not intersect:
+            self.cbca_intersect_config(False)
         if refine_ext:
             self.refine_ext_config(**dict(refine_ext))
         self.n = 0
@@ -512,6 +521,20 @@ class StereoBatch:
         out = np.empty(self.shape[:2], np.uint8)
         st = self._lib.sm_get_cbca_dw_mask(self._ctx, _capi.ptr(out))
         _capi.check(self._lib, self._ctx, st, "get_cbca_dw_mask")
+        return out
+
+    def cbca_intersect_config(self, intersect: bool = True):
+        """sm_cbca_intersect_config: False runs "CBCA" without arm intersection (the view's own arms, one area
+        per pixel), from the next run on."""
+        st = self._lib.sm_cbca_intersect_config(self._ctx, int(bool(intersect)))
+        _capi.check(self._lib, self._ctx, st, "cbca_intersect_config")
+
+    def get_cbca_area(self, view: int = 0) -> np.ndarray:
+        """sm_get_cbca_area: the first pair's support areas [H][W] (int32) of the last run without arm
+        intersection."""
+        out = np.empty(self.shape[:2], np.int32)
+        st = self._lib.sm_get_cbca_area(self._ctx, int(view), _capi.ptr(out))
+        _capi.check(self._lib, self._ctx, st, "get_cbca_area")
         return out
 
     def refine_ext_config(self, do_pkr: bool = False, pkr_ratio: float = _capi.REFINE_EXT_DEFAULTS[0],

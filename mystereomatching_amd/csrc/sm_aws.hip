@@ -27,7 +27,7 @@
 //                  broadcast) and does mul, add, mul, add, separately rounded (-ffp-contract=off),
 //                  which the compiler packs two u at a time (v_pk_mul_f32 / v_pk_add_f32).
 //                  76 VGPRs, 35.2 KB LDS, no scratch: four blocks (16 waves) per CU.
-// This file is compiled as part of sm_gf.hip's translation unit (included at its end; Makefile).
+// A translation unit of its own (it shares no code with the guided filter).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -28,7 +28,7 @@
 // The variance plane is two 19 x 19 filters of integers <= 255^2: their sums are exact (below
 // 2^25, in uint32 here as in the reference's doubles), so the order of the taps is free and one
 // thread per pixel sums the window directly.
-// This file is compiled as part of sm_gf_cv.hip's translation unit (included at its end; Makefile).
+// A translation unit of its own (it shares no code with the guided filter).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -588,7 +588,7 @@ struct CbLine {
 //    nothing; the allocations carry tail pads for the tiles that straddle the end), the arm
 //    gathers and own-arm loads through fixed per-plane resources with a uniform row offset;
 //  * CHECK = false when the host has proven that every dividend is 0 or >= 2^-110 (iteration
-//    0's normalisation of costs >= 2^-24: cbca_div_safe in sm_capi.cpp), so the tiny-dividend
+//    0's normalisation of costs >= 2^-24: cbca_div_safe in sm_validate.cpp), so the tiny-dividend
 //    test of the area division is dropped.
 #ifndef SM_CB_T_NSV
 #define SM_CB_T_NSV 7
@@ -1900,13 +1900,6 @@ void launch_cbca(const CbcaArgs& a, bool horiz, int mode, int n, hipStream_t st)
 }
 
 }  // namespace sm
-
-// CBCA()'s double-window branch (cbca_double_win: the mask and the selection of combine2Vm_4) is part of this
-// translation unit: the host-side sanitizer build of the C ABI (tests/test_sanitizers.py) links a fixed list of
-// kernel objects, so a new launcher has to live in one of them.
-#include "sm_cbca_dw.hip"
-// ... and so is cbca_core without arm intersection (cbca_intersect == false: prefix and window kernels)
-#include "sm_cbca_ni.hip"
 
 #if SM_CB_NSV_TRACE
 // diagnostic builds only: [block][wave][phase] cycle sums of the last NsV2 launch (phase 7 = tiles)

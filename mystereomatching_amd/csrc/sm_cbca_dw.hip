@@ -2,14 +2,14 @@
 // aggregated twice, with the arms of window 1 (into a second volume) and of window 0 (in place), and
 // combine2Vm_4 (cpp:4273-4331) gives every pixel whose neighbourhood has only short window-0 arms the
 // large-window costs.  The two aggregations are the sweeps above with a second arm set; this file holds the
-// mask and the selection.  Included at the end of sm_cbca.hip (one translation unit, one object).
+// mask and the selection.  The sweeps are sm_cbca.hip's; this file is a translation unit of its own.
 //
 // k_dw_mask    arm_Lst(v, u) = the longest of the four window-0 arms of the LEFT image (HVL[0], cpp:4287),
 //              cv::boxFilter 3 x 3 (normalised, BORDER_REFLECT_101, double sums, (float)(sum * (1.0 / 9))),
 //              arm_Mask = filtered < armLthres.  Arm lengths are integers, so the nine-term sum is exact in
 //              any order, and the float form is non-decreasing in it: the host turns the threshold into
 //              the integer isum with `filtered < thres  <=>  sum < isum` for every sum the arm kernel can
-//              produce (dw_int_threshold, sm_capi.cpp; 45 for the reference's 5).  One thread per pixel,
+//              produce (dw_int_threshold, sm_validate.cpp; 45 for the reference's 5).  One thread per pixel,
 //              one byte out; reads 2 planes x 9 taps (8 B per pixel from HBM, the rest from L2).
 // k_dw_select  vm[view](v, u, :) = vm2[view](v, u, :) where the mask is set (`x * 0 + y * 1` on finite
 //              costs: a copy).  A thread owns one 16-byte piece of one pixel's D floats and returns after
@@ -18,6 +18,11 @@
 //              the same byte: one request per wave or fewer).  D % 4 == 0: every piece is an aligned
 //              dwordx4.  Else a pixel's floats start at any dword: the pieces are the aligned dwordx4s
 //              inside [p D, p D + D) plus a scalar head and a scalar tail of up to three floats each.
+#include <hip/hip_runtime.h>
+
+#include "sm_device.h"
+#include "sm_kernels.h"
+
 namespace sm {
 
 __device__ __forceinline__ int dw_arm_max(const uint32_t* __restrict__ p0, const uint32_t* __restrict__ p1, size_t i) {

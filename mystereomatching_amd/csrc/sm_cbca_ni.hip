@@ -1,7 +1,7 @@
 // sm_cbca_ni.hip — cbca_core without arm intersection (Parameters::cbca_intersect == false, cpp:5585-5666): the
 // cross-based aggregation of Zhang et al.  The support region of a pixel comes from the view's own image's arms
 // (HVL[LOR]) and is the same for every disparity, so one integer area per pixel replaces one per volume element.
-// Included at the end of sm_cbca.hip (one translation unit, one object).
+// A translation unit of its own: it shares no kernel with the intersecting sweeps of sm_cbca.hip.
 //
 // One 1-D pass (gen1DCumu cpp:3896-3926, then cal1DCost h:1643-1715) is two kernels, the plain form:
 //
@@ -24,6 +24,11 @@
 // VEC = 4 (16-byte accesses) where D % 4 == 0, else 1.  x + head never passes the line's end (the arm kernel
 // stops at the image border); the kernels clamp it all the same, so no arm word can make them read outside
 // the volume.
+#include <hip/hip_runtime.h>
+
+#include "sm_device.h"
+#include "sm_kernels.h"
+
 namespace sm {
 
 constexpr int NI_TILE = 8;

@@ -1,6 +1,6 @@
 // sm_cost_ext.hip — the cost measures beyond k_cost's four: "SD", "BT", "grad",
-// "TruncAD", "adGrad" and "ADCensusGrad" of costCalculate (cpp:954-987).  Compiled as part of
-// sm_pyramid.hip's translation unit (see the note at its end).
+// "TruncAD", "adGrad" and "ADCensusGrad" of costCalculate (cpp:954-987).  A translation unit of its
+// own; the per-element cost terms it shares with k_cost are sm_cost_elem.h's.
 //
 // k_cost_ext<M> has k_cost's block shape: one row segment of np focus pixels x D.  The moving
 // pixels [u0 - (D - 1), u0 + np) (view 1: [u0, u0 + np + D - 1)) are staged in LDS once per block,

@@ -28,7 +28,7 @@
 // Four launches per view: H forward (vm -> c1), H backward (vm, c1 -> A), V forward (A -> T),
 // V backward (A, T -> vm, times SolveAll's weight when fused): 8 + 12 + 8 + 12 = 40 B per element
 // and two scratch volumes (c1 and T share one).
-// This file is compiled as part of sm_sgm.hip's translation unit (included at its end; Makefile).
+// A translation unit of its own; only the wave-per-line layout is sm_sgm.hip's.
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>

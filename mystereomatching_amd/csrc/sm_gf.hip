@@ -376,8 +376,3 @@ void launch_gf(const GfArgs& a, int n, hipStream_t st) {
 }
 
 }  // namespace sm
-
-// The "AWS" aggregation kernels are part of this translation unit: the host-side sanitizer build
-// of the C ABI (tests/test_sanitizers.py) links a fixed list of kernel objects, so a new launcher
-// has to live in one of them.
-#include "sm_aws.hip"

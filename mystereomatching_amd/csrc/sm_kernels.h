@@ -353,7 +353,7 @@ struct DwArgs {
     size_t pix0;                // first pixel of the launch: first pair * H * W
     int H, W, D;
     int isum;                   // arm_Mask = sum of the nine maxima < isum: armLthres (cpp:4297) in the integer
-                                // form the host derives for it (dw_int_threshold, sm_capi.cpp)
+                                // form the host derives for it (dw_int_threshold, sm_validate.cpp)
 };
 void launch_dw_mask(const DwArgs& a, int n, hipStream_t st);     // H, W >= 2
 void launch_dw_select(const DwArgs& a, int n, hipStream_t st);

@@ -122,8 +122,3 @@ void launch_solve_all_pyr(const PyrArgs& a, hipStream_t st) {
 }
 
 }  // namespace sm
-
-// The cost measures of sm_cost_ext.hip (k_cost_ext, launch_cost_ext) are part of this translation
-// unit: the host-side sanitizer build of the C ABI (tests/test_sanitizers.py) links a fixed list of
-// kernel objects, so a new launcher has to live in one of them.
-#include "sm_cost_ext.hip"

@@ -7,14 +7,15 @@
 // W x H x D volume passes; every stage that reads neighbours is Jacobi (reads the previous map,
 // writes a new one) exactly like the reference's dp_res / DpCopy / OpenCV's copied source.
 //
-// Mapping: one thread per pixel, 256-thread blocks over [pair][row-tile][col-tile] 64 x 4 tiles so
-// a wave covers one 64-pixel row segment (coalesced int16 accesses); valid pixels exit at once,
+// Mapping (sm_refine_map.h): one thread per pixel, 256-thread blocks over [pair][row-tile][col-tile] 64 x 4
+// tiles so a wave covers one 64-pixel row segment (coalesced int16 accesses); valid pixels exit at once,
 // the holes (typically 5-20 %) do the searches.  Maps and arms are re-read from L2 / MALL.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sm_device.h"
 #include "sm_kernels.h"
+#include "sm_refine_map.h"
 
 namespace sm {
 
@@ -24,29 +25,6 @@ __device__ __forceinline__ int colour_dif(uint32_t x, uint32_t y) {  // max_c |I
     return max(max(abs((int)(x & 0xff) - (int)(y & 0xff)), abs((int)((x >> 8) & 0xff) - (int)((y >> 8) & 0xff))),
                abs((int)((x >> 16) & 0xff) - (int)((y >> 16) & 0xff)));
 }
-
-constexpr int TX = 64, TY = 4;
-
-struct Pix {
-    int b, v, u;
-    bool ok;
-};
-
-__device__ __forceinline__ Pix pixel_of(int H, int W) {
-    const int tiles_x = (W + TX - 1) / TX, tiles_y = (H + TY - 1) / TY;
-    const int per_pair = tiles_x * tiles_y;
-    const int blk = blockIdx.x;
-    Pix p;
-    p.b = blk / per_pair;
-    const int t = blk - p.b * per_pair;
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    p.u = tx * TX + (int)(threadIdx.x & (TX - 1));
-    p.v = ty * TY + (int)(threadIdx.x / TX);
-    p.ok = p.u < W && p.v < H;
-    return p;
-}
-
-dim3 grid_of(int n, int H, int W) { return dim3((unsigned)(n * ((W + TX - 1) / TX) * ((H + TY - 1) / TY))); }
 
 // LRConsistencyCheck_normal (cpp:2262-2282), LOR = 0, in place: d < 0, u - d < 0 or
 // |d - D2(u - d)| > LRmaxDiff  ->  -1.  The int difference is compared as a float (int > float).
@@ -240,5 +218,3 @@ void launch_median3(const int16_t* src, int16_t* dst, int n, int H, int W, hipSt
 }
 
 }  // namespace sm
-
-#include "sm_refine_ext.hip"   // refine()'s peak-ratio check, background fill and sub-pixel map

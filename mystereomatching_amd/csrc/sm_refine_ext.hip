@@ -2,7 +2,7 @@
 // (sm_refine_ext_config): the peak-ratio check (Do_calPKR: calPKR + signDp_UsingPKR, cpp:4087-4140), the
 // background fill (Do_bgIpol: BGIpol + backgroundInterpolateCore, cpp:7323-7338, 7011-7043) and the sub-pixel
 // map (Do_subpixelEnhancement: subpixelEnhancement + medianBlur(SE, SE, 3), cpp:6138-6167, 1482-1495).
-// Compiled into sm_refine.o (included at the end of sm_refine.hip, whose pixel mapping it shares).
+// A translation unit of its own; it shares sm_refine.hip's pixel mapping (sm_refine_map.h).
 //
 // k_pkr          the one volume pass.  16 lanes (one DPP row) serve a pixel: each keeps the two smallest of the
 //                costs it reads (lane l the disparities 64 c + 4 l .. + 3 of every chunk c with 16-byte loads
@@ -14,7 +14,14 @@
 //                right, an inclusive scan of (constant | min-with-constant) maps per chunk and one carried value.
 // k_subpixel     three gathered costs per pixel, both forms of the result.
 // k_median3_f32  k_median3's network on floats.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
 #include <cfloat>
+
+#include "sm_device.h"
+#include "sm_kernels.h"
+#include "sm_refine_map.h"
 
 namespace sm {
 

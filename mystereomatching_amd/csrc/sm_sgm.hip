@@ -1044,9 +1044,3 @@ void launch_sgm_path(const SgmArgs& a, int mode, int n, hipStream_t st) {
 }
 
 }  // namespace sm
-
-// The "FIF" aggregation sweeps (the same wave-per-line recurrence without the path minimum) are
-// part of this translation unit: the host-side sanitizer build of the C ABI
-// (tests/test_sanitizers.py) links a fixed list of kernel objects, so a new launcher has to live
-// in one of them.
-#include "sm_fif.hip"

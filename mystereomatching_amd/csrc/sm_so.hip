@@ -260,8 +260,3 @@ void launch_so(const SoArgs& a, hipStream_t st) {
 }
 
 }  // namespace sm
-
-// dispOptimize's other branch, the candidate-disparity selection (Do_vmTop), is part of this translation unit:
-// the host-side sanitizer build of the C ABI (tests/test_sanitizers.py) links a fixed list of kernel objects, so
-// a new launcher has to live in one of them.
-#include "sm_vmtop.hip"

@@ -1,7 +1,7 @@
 // sm_vmtop.hip — dispOptimize's Do_vmTop branch (stereoMatching.cpp:1108-1128): instead of the plain WTA every
 // pixel keeps the vmTop_Num cheapest disparities within a factor vmTop_thres of its minimum
 // (selectTopCostFromVolumn, h:2405-2461) and chooses among them from its neighbours' candidates
-// (genDispFromTopCostVm2, cpp:1514-1885).
+// (genDispFromTopCostVm2, cpp:1514-1885).  A translation unit of its own, beside "so" (sm_so.hip) and WTA.
 //
 // k_vmtop_select   the hot path: one read of the volume.  A group of 16 lanes (one DPP row) holds one pixel's
 //                  D costs in registers, lane l the disparities 64 c + 4 l .. + 3 of every 64-chunk c (one

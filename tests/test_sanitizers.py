@@ -11,7 +11,8 @@ run on inputs that reach the code's edges:
     corrupt and short IDAT streams, bad CRCs, random bytes.  The reference's answer to an
     unreadable image is an error message and exit (main_.cpp:108-112, h:1741-1742); here imread
     returns an empty Mat;
-  * the C-ABI's host side (csrc/sm_capi.cpp, host code sanitized with hipcc -Xarch_host) without a
+  * the C-ABI's host side (csrc/sm_capi.cpp and the other host sources the library's Makefile
+    lists, host code sanitized with hipcc -Xarch_host) without a
     GPU: parameter validation, null / out-of-range arguments, calErr, tests/cpp/capi_host_check.cpp.
 """
 import os
@@ -171,20 +172,26 @@ def test_imread_sanitized(tmp_path):
 @pytest.mark.skipif(not os.path.exists(HIPCC) or not os.path.isdir(os.path.join(CSRC, "build")),
                     reason="needs hipcc and the library's kernel objects (build())")
 def test_capi_host_sanitized(tmp_path):
-    objs = [os.path.join(CSRC, "build", f"{s}.o") for s in
-            ("sm_kernels", "sm_cbca", "sm_sgm", "sm_refine", "sm_pyramid", "sm_so", "sm_gf", "sm_gf_cv", "sm_nl",
-             "sm_nl_mst", "sm_nl_walk")]
+    # the library's kernel objects and host sources, as its Makefile lists them
+    def listed(target):
+        return _run(["make", "-s", "--no-print-directory", "-C", CSRC, target]).stdout.split()
+    objs = [os.path.join(CSRC, o) for o in listed("list-kernel-objects")]
+    host = listed("list-host-sources")
+    assert objs and "sm_capi.cpp" in host
     if not all(os.path.exists(o) for o in objs):
         pytest.skip("kernel objects not built")
-    capi_o, chk_o, exe = (str(tmp_path / n) for n in ("capi_san.o", "chk.o", "capi_host_check"))
+    chk_o, exe = (str(tmp_path / n) for n in ("chk.o", "capi_host_check"))
     # host code sanitized, device code as shipped (GPU sanitizers are not available on this pool)
-    _run([HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w",
-          "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-          "-Xarch_host", "-fno-sanitize-recover=all", "-c", os.path.join(CSRC, "sm_capi.cpp"), "-o", capi_o])
+    host_o = []
+    for src in host:
+        host_o.append(str(tmp_path / (os.path.splitext(src)[0] + "_san.o")))
+        _run([HIPCC, "--offload-arch=gfx950", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w",
+              "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
+              "-Xarch_host", "-fno-sanitize-recover=all", "-c", os.path.join(CSRC, src), "-o", host_o[-1]])
     clang = "/opt/rocm/lib/llvm/bin/clang++"
     _run([clang, "-std=c++17", *SAN, f"-I{INC}", "-I/opt/rocm/include", "-D__HIP_PLATFORM_AMD__", "-c",
           os.path.join(ROOT, "tests", "cpp", "capi_host_check.cpp"), "-o", chk_o])
-    _run([HIPCC, "--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize", chk_o, capi_o, *objs,
+    _run([HIPCC, "--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize", chk_o, *host_o, *objs,
           "-o", exe])
     # (the HIP runtime's own allocations at exit are not this code's: leak checking off here)
     env = dict(ENV, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1")

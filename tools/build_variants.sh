@@ -1,8 +1,11 @@
 #!/bin/bash
 # Builds tuning variants of libsm_hip.so that differ only in one source file's compile-time
-# switches (default sm_cbca.hip; SRC=sm_kernels, SRC=sm_sgm, SRC=sm_capi (.cpp), ... for the others), for same-box A/B
+# switches (default sm_cbca.hip; SRC=sm_kernels, SRC=sm_sgm, SRC=sm_run (.cpp), ... for the others), for same-box A/B
 # runs on one GPU box (tools/ab_inproc.py; tools/abvar/ travels with gpurun -- delete it after the A/B
 # so that later pushes, the driver's included, do not carry it).
+# The host files' switches: SM_FUSE_SOLVE_ALL, SM_STAGGER_STAGE and SM_UP_EARLY are read by sm_run.cpp
+# (SRC=sm_run), SM_NL_PIPE by sm_capi.cpp (SRC=sm_capi).
+# The library's objects are the Makefile's (its list-kernel-objects and list-host-sources targets).
 # usage: [SRC=sm_cbca] tools/build_variants.sh NAME "-DSWITCH=value ..." [NAME2 "DEFS2" ...]
 set -e
 SRC=${SRC:-sm_cbca}
@@ -17,7 +20,8 @@ while [ $# -ge 2 ]; do
   /opt/rocm/bin/hipcc $FLAGS $defs -c $SRC.$EXT -o build/var/${SRC}__$name.o &
 done
 wait
-OBJS="build/sm_kernels.o build/sm_cbca.o build/sm_sgm.o build/sm_refine.o build/sm_pyramid.o build/sm_so.o build/sm_gf.o build/sm_gf_cv.o build/sm_nl.o build/sm_nl_mst.o build/sm_nl_walk.o build/sm_capi.o"
+OBJS="$(make -s --no-print-directory list-kernel-objects | tr '\n' ' ')"
+for s in $(make -s --no-print-directory list-host-sources); do OBJS="$OBJS build/${s%.cpp}.o"; done
 for o in build/var/${SRC}__*.o; do
   name=${o#build/var/${SRC}__}; name=${name%.o}
   objs=${OBJS/build\/$SRC.o/$o}

@@ -79,18 +79,15 @@ sm_status download_sync(sm_ctx* c, void* dst, const void* src, size_t bytes) {
 void free_all(sm_ctx* c) {
     for (void* q : c->allocs) hipFree(q);
     c->allocs.clear();
-    if (c->nl_st) {
-        hipStreamSynchronize(c->nl_st);
-        hipStreamDestroy(c->nl_st);
-        c->nl_st = nullptr;
-    }
-    for (hipEvent_t* ev : {c->nl_ev_set, c->nl_ev_opt})
-        for (int i = 0; i < 2; i++)
-            if (ev[i]) {
-                hipEventSynchronize(ev[i]);
-                hipEventDestroy(ev[i]);
-                ev[i] = nullptr;
-            }
+    // every stream is drained and destroyed (the main stream last) before the events its work recorded or waited for
+    for (hipStream_t* st : {&c->nl_st, &c->cst, &c->xst[0], &c->xst[1], &c->xst[2], &c->st})
+        if (*st) {
+            hipStreamSynchronize(*st);
+            hipStreamDestroy(*st);
+            *st = nullptr;
+        }
+    for (hipEvent_t e : c->events) hipEventDestroy(e);
+    c->events.clear();
     if (c->nl_offs_h) {
         hipHostFree(c->nl_offs_h);
         c->nl_offs_h = nullptr;
@@ -100,30 +97,8 @@ void free_all(sm_ctx* c) {
         if (r.stop) hipEventDestroy(r.stop);
     }
     for (auto e : c->free_events) hipEventDestroy(e);
-    for (auto e : c->xev) hipEventDestroy(e);
-    c->xev.clear();
-    if (c->cst) {
-        hipStreamSynchronize(c->cst);
-        hipStreamDestroy(c->cst);
-        c->cst = nullptr;
-    }
-    for (hipEvent_t* ev : {&c->ev_dl[0], &c->ev_dl[1], &c->ev_up[0], &c->ev_up[1], &c->ev_in[0], &c->ev_in[1]})
-        if (*ev) {
-            hipEventDestroy(*ev);
-            *ev = nullptr;
-        }
-    if (c->ev_run) hipEventDestroy(c->ev_run);
-    if (c->ev_copy) hipEventDestroy(c->ev_copy);
-    if (c->ev_copy2) hipEventDestroy(c->ev_copy2);
-    c->ev_run = c->ev_copy = c->ev_copy2 = nullptr;
-    for (auto& x : c->xst)
-        if (x) {
-            hipStreamDestroy(x);
-            x = nullptr;
-        }
     c->recs.clear();
     c->free_events.clear();
-    if (c->st) hipStreamDestroy(c->st);
 }
 
 }  // namespace
@@ -283,11 +258,6 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         c->fuse_cost_scan = p->fuse_cost_scan != 0;
         if ((s = apply_schedule(c, p->num_streams, p->sub_batch))) return s;
         if ((s = aws_alloc_bands(c))) return s;
-        for (int i = 0; i < 16; i++) {
-            hipEvent_t e;
-            HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->xev.push_back(e);
-        }
     }
     if ((s = dalloc(c, &c->luts, 2048))) return s;
     HIP_TRY(c, hipMemcpyAsync(c->luts, c->lut_a, sizeof(c->lut_a), hipMemcpyHostToDevice, c->st));
@@ -321,15 +291,14 @@ sm_status sm_cost_calculate(sm_ctx* c) {
     sm_status s = check(c);
     if (s) return s;
     if (c->stage < 1) return fail(c, SM_ESTATE, "sm_cost_calculate before sm_set_images");
-    const int n = c->n_loaded;
-    const Bufs B = at(c, 0);
-    if ((s = run_prep(c, n, B))) return s;
-    if ((s = run_cost(c, n, 0, B))) return s;
-    if (right_view(c->p) && (s = run_cost(c, n, 1, B))) return s;
+    const Group G = at(c, 0, c->n_loaded, c->st);
+    if ((s = run_prep(c, G))) return s;
+    if ((s = run_cost(c, 0, G))) return s;
+    if (right_view(c->p) && (s = run_cost(c, 1, G))) return s;
     if (c->p.aggregation == SM_AGG_CBCA)
         for (int v = 0; v < n_views(c->p); v++)
-            if ((s = run_cbca(c, n, v, false, 1.0f, B))) return s;
-    if ((s = run_other_agg(c, n, B))) return s;
+            if ((s = run_cbca(c, v, false, 1.0f, G))) return s;
+    if ((s = run_other_agg(c, G))) return s;
     c->stage = 2;
     return SM_OK;
 }
@@ -342,7 +311,7 @@ sm_status sm_solve_all(sm_ctx* c, int32_t py_lev, float reg_lambda) {
     const float m = 1 + reg_lambda;
     const float w = (float)(1. / (double)m);  // Mat::inv of the 1x1 regMat (cpp:2164)
     for (int v = 0; v < n_views(c->p); v++)   // img_n = Do_refine ? 2 : 1 (cpp:2178)
-        if ((s = run_scale(c, c->n_loaded, v, w, at(c, 0)))) return s;
+        if ((s = run_scale(c, v, w, at(c, 0, c->n_loaded, c->st)))) return s;
     c->stage = 3;
     return SM_OK;
 }
@@ -454,7 +423,7 @@ sm_status sm_solve_all_pyr(sm_ctx* const* levels, int32_t py_lvl, float reg_lamb
     for (int v = 0; v < n_views(c->p); v++) {
         for (int l = 0; l < py_lvl; l++) a.vm[l] = v == 0 ? levels[l]->vm0 : levels[l]->vm1;
         const double bytes = (double)a.n * c->nvol * 8.0;
-        if ((s = timed(c, v == 0 ? "solve_all_pyr" : "solve_all_pyr_r", bytes, [&] { sm::launch_solve_all_pyr(a, c->st); })))
+        if ((s = timed(c, c->st, v == 0 ? "solve_all_pyr" : "solve_all_pyr_r", bytes, [&] { sm::launch_solve_all_pyr(a, c->st); })))
             return s;
     }
     c->stage = 3;
@@ -504,7 +473,7 @@ sm_status sm_disp_optimize(sm_ctx* c, int16_t* disp_out) {
     if (c->stage < 2 || c->stage > 3) return fail(c, SM_ESTATE, "sm_disp_optimize must follow sm_cost_calculate / sm_solve_all");
     if ((s = wait_copy(c))) return s;
     for (int v = 0; v < opt_views(c->p); v++)   // num (cpp:1054, 1093, 1110)
-        if ((s = run_optimize(c, c->n_loaded, v, at(c, 0)))) return s;
+        if ((s = run_optimize(c, v, at(c, 0, c->n_loaded, c->st)))) return s;
     c->stage = 4;
     c->rx_vol_ok = true;
     if (disp_out) return sm_download_disp(c, 1, disp_out);
@@ -519,7 +488,7 @@ sm_status sm_refine(sm_ctx* c, int16_t* disp_out) {
     if (refine_reads_volume(c) && c->p.optimization == SM_OPT_SGM && !c->p.keep_final_volume && !c->vt_on && !c->rx_vol_ok)
         return fail(c, SM_ESTATE, "sm_refine: do_pkr / do_subpixel were switched on after sm_disp_optimize (SGM kept no path sum)");
     if ((s = wait_copy(c))) return s;
-    if ((s = run_refine(c, c->n_loaded, at(c, 0)))) return s;
+    if ((s = run_refine(c, at(c, 0, c->n_loaded, c->st)))) return s;
     c->stage = 5;
     if (disp_out) return sm_download_disp(c, 1, disp_out);
     return SM_OK;

@@ -1,7 +1,9 @@
 // sm_ctx.h — internal to the host side of libsm_hip.so (not installed): the context behind the C ABI's opaque
-// sm_ctx and the helpers every host file uses -- error returns, the profiling bracket around a launch, device
-// memory through the context's allocation registry, a group's buffer pointers, the entry checks -- and the
-// declarations of what crosses the host files.  None of these names is exported (-fvisibility=hidden).
+// sm_ctx and the helpers every host file uses -- error returns, the profiling bracket around a launch on a given
+// stream, device memory and events through the context's registries, the group descriptor every stage driver takes
+// (a group's buffer pointers, pairs, stream and lane), the entry checks -- and the declarations of what crosses the
+// host files.  c->st is the context's main stream from sm_create to sm_destroy and nothing else: where a launch goes
+// is the descriptor's business.  None of these names is exported (-fvisibility=hidden).
 #pragma once
 #include "../../include/sm_capi.h"
 
@@ -28,9 +30,10 @@ struct ProfStat {
 struct sm_ctx {
     sm_params p{};
     int device = 0;
-    hipStream_t st = nullptr;
+    hipStream_t st = nullptr;   // the main stream (sm_create .. sm_destroy; never reassigned)
     std::string err;
     std::vector<void*> allocs;  // every device buffer the context owns (dalloc / dfree)
+    std::vector<hipEvent_t> events;   // every untimed event the context owns (use_event)
     int cap = 1;
     size_t npix = 0, nvol = 0;
     size_t vtail = 0;           // floats of tail pad after each volume's cap * nvol
@@ -138,17 +141,16 @@ struct sm_ctx {
     uint8_t* nl_walk = nullptr;             // tree-walk work space (sm::nl_walk_scratch_bytes)
     int* nl_offs = nullptr;                 // round offsets + error flags (device)
     int* nl_offs_h = nullptr;               // the same, page-locked host copy
-    int nl_set = 0;                         // record / table set of the next call (double-buffered)
-    int nl_opt_set = 0;                     // pipelined NL: the set the current call's optimiser reads
+    int nl_set = 0;                         // record / table set the next run_nl takes (double-buffered)
     hipStream_t nl_st = nullptr;        // NL front (median, edge weights, spanning trees, tree walk)
-    hipEvent_t nl_ev_set[2] = {nullptr, nullptr};   // the last filter reading each record / table set (on c->st)
+    hipEvent_t nl_ev_set[2] = {nullptr, nullptr};   // the last filter reading each record / table set (group's stream)
     // pipelined NL front (sm_run with NL + SGM, one view): the call's prep and cost volume also run
     // on nl_st, into a cost volume and penalty flags of the call's set, so they overlap the
-    // previous call's filter and SGM on c->st
+    // previous call's filter and SGM on the main stream
     bool nl_pipe = false;
     float* nl_vc = nullptr;                 // [2][cap][nvol] cost volumes (filter input)
     uint8_t* nl_fl = nullptr;               // [2][cap][npix] SGM penalty flags
-    hipEvent_t nl_ev_opt[2] = {nullptr, nullptr};   // the last optimiser reading each set (on c->st)
+    hipEvent_t nl_ev_opt[2] = {nullptr, nullptr};   // the last optimiser reading each set (main stream)
     double* nl_table = nullptr; // [256]
     double* nl_val = nullptr;   // [cap][nvol]
     double* nl_oup = nullptr;   // [cap][npix] the ones channel: up sums
@@ -175,7 +177,7 @@ struct sm_ctx {
     int dl_count = 0;
     hipEvent_t ev_up[2] = {};   // an async upload's copies done: main stream, side stream
     hipEvent_t ev_in[2] = {};   // a pipelined run's group k has read its input images: recorded after the cost
-                                // volume, or (cost_scan_fused) after the last view's first CBCA sweep (in_ev)
+                                // volume, or (cost_scan_fused) after the last view's first CBCA sweep (Group::in_ev)
     // (an early async upload goes on the null stream: the runtime spreads streams round-robin over
     // GPU_MAX_HW_QUEUES (4) in-order hardware queues, and a fifth stream of the context shared one
     // with a group or the map copies, whose kernels / copies the upload then waited behind; the
@@ -189,10 +191,11 @@ struct sm_ctx {
     int place_trials = 0;       // > 1: the first sm_run chooses among that many volume sets (place_volumes)
     std::vector<double> place_ms;   // the trials' pipeline times (sm_placement_trials_ms)
     int place_best = -1;
-    std::vector<hipEvent_t> xev;                        // stagger / join events
-    hipEvent_t in_ev = nullptr;   // a pipelined group whose first CBCA sweep reads the input images: its "inputs
-                                  // read" event, recorded by run_cbca after the last view's first sweep
-    hipEvent_t stagger_ev = nullptr;                    // SM_STAGGER_STAGE 1: recorded after the first CBCA sweep
+    // sm_run's schedule events
+    hipEvent_t ev_start = nullptr;     // the main stream as the call found it: the side streams start after it
+    hipEvent_t ev_stagger[8] = {};     // group k may be followed by group k + 1 (slot k % 8)
+    hipEvent_t ev_join[3] = {};        // side stream i has finished its groups: the main stream waits (also join_all)
+    hipEvent_t ev_side = nullptr;      // sm_download_disp_async: the side stream as the copy stream must find it
     // profiling
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -221,28 +224,28 @@ inline sm_status hip_fail(sm_ctx* c, hipError_t e, const char* where) {
 hipEvent_t get_event(sm_ctx* c);
 int kernel_id(sm_ctx* c, const char* name, double bytes);
 
-// Brackets one launch with events when profiling is on.
+// Brackets one launch on stream `st` with events when profiling is on.
 template <typename F>
-sm_status timed(sm_ctx* c, const char* name, double bytes, F&& launch) {
+sm_status timed(sm_ctx* c, hipStream_t st, const char* name, double bytes, F&& launch) {
     ProfRec r{-1, nullptr, nullptr};
     if (c->prof) {
         r.kernel = kernel_id(c, name, bytes);
         r.start = get_event(c);
         r.stop = get_event(c);
-        if (r.start) hipEventRecord(r.start, c->st);
+        if (r.start) hipEventRecord(r.start, st);
     }
     launch();
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(c, e, name);
     if (c->prof && r.start && r.stop) {
-        hipEventRecord(r.stop, c->st);
+        hipEventRecord(r.stop, st);
         c->recs.push_back(r);
     }
     return SM_OK;
 }
 template <typename F>   // (a name built at the call: base + view / window suffix)
-sm_status timed(sm_ctx* c, const std::string& name, double bytes, F&& launch) {
-    return timed(c, name.c_str(), bytes, launch);
+sm_status timed(sm_ctx* c, hipStream_t st, const std::string& name, double bytes, F&& launch) {
+    return timed(c, st, name.c_str(), bytes, launch);
 }
 
 // Device memory goes through these two: dalloc records what it returns in c->allocs, dfree releases one
@@ -267,8 +270,18 @@ void dfree(sm_ctx* c, T*& ptr) {
     ptr = nullptr;
 }
 
-// Device pointers of pair `off` onward (the kernels index pairs from their base pointers).
-struct Bufs {
+// Events other than profiling's go through this: the first use creates the event (without timing) and records
+// it in c->events; free_all (sm_destroy) destroys whatever is recorded there.
+inline sm_status use_event(sm_ctx* c, hipEvent_t& ev) {
+    if (ev) return SM_OK;
+    HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    c->events.push_back(ev);
+    return SM_OK;
+}
+
+// A group of pairs as a stage driver sees it: the device pointers of pair `off` onward (the kernels index pairs
+// from their base pointers), how many pairs, and the stream the group's launches go to.
+struct Group {
     uint8_t* bgr;
     uint8_t* gray;
     ulonglong2* code;
@@ -286,30 +299,55 @@ struct Bufs {
     uint32_t* px;
     uint32_t* pxh;
     uint32_t* pxv;
+    int off, n;        // the first pair and the number of pairs
+    hipStream_t st;
+    int lane;          // 0: the main stream, i + 1: xst[i] (what exists once per stream is indexed by it: aws_band)
+    // what run_cbca records for sm_run (null: nothing): after the last view's first sweep, the last reader of the
+    // group's input images where that sweep computes the costs; after view 0's first sweep, where the next group starts
+    hipEvent_t in_ev, stagger_ev;
+
+    float* vm(int view) const { return view == 0 ? vm0 : vm1; }
+    int16_t* map(int view) const { return view == 0 ? disp : disp1; }
+    uint8_t* penalty(int view) const { return view == 0 ? flags : flags1; }
+    // the group's slice of a per-pair scratch array of `stride` elements per pair
+    template <typename T>
+    T* slice(T* base, size_t stride) const {
+        return base + (size_t)off * stride;
+    }
+    // a view's profile name: "gf" / "gf_r"
+    static std::string name(const char* base, int view) { return std::string(base) + (view == 0 ? "" : "_r"); }
 };
 
-inline Bufs at(const sm_ctx* c, int off) {
-    const size_t o = (size_t)off, np = c->npix, nv = c->nvol;
-    Bufs b;
-    b.bgr = c->bgr + o * 2 * np * 3;
-    b.gray = c->gray + o * 2 * np;
-    b.code = c->code + o * 2 * np;
-    b.arms = c->arms + o * 2 * 2 * np * 4;
-    b.vm0 = c->vm0 + o * nv;
-    b.vm1 = c->vm1 ? c->vm1 + o * nv : nullptr;
-    b.acc = c->acc ? c->acc + o * nv : nullptr;
-    b.ck = c->ck ? c->ck + o * c->ck_pair : nullptr;
-    b.lx = c->lx ? c->lx + o * nv : nullptr;
-    b.disp = c->disp + o * np;
-    b.disp1 = c->disp1 ? c->disp1 + o * np : nullptr;
-    b.disp_tmp = c->disp_tmp ? c->disp_tmp + o * np : nullptr;
-    b.flags = c->flags + o * np;
-    b.flags1 = c->flags1 ? c->flags1 + o * np : nullptr;
-    b.px = c->px + o * 2 * np;
-    b.pxh = c->px + (c->cap + o) * 2 * np;
-    b.pxv = c->px + (2 * c->cap + o) * 2 * np;
-    return b;
+// Pairs [off, off + n) on stream `st` (lane: see Group; the reference-ordered entry points run on the main stream).
+inline Group at(const sm_ctx* c, int off, int n, hipStream_t st, int lane = 0) {
+    const size_t np = c->npix, nv = c->nvol;
+    Group g{};
+    g.off = off;
+    g.n = n;
+    g.st = st;
+    g.lane = lane;
+    g.bgr = g.slice(c->bgr, 2 * np * 3);
+    g.gray = g.slice(c->gray, 2 * np);
+    g.code = g.slice(c->code, 2 * np);
+    g.arms = g.slice(c->arms, 2 * 2 * np * 4);
+    g.vm0 = g.slice(c->vm0, nv);
+    g.vm1 = c->vm1 ? g.slice(c->vm1, nv) : nullptr;
+    g.acc = c->acc ? g.slice(c->acc, nv) : nullptr;
+    g.ck = c->ck ? g.slice(c->ck, c->ck_pair) : nullptr;
+    g.lx = c->lx ? g.slice(c->lx, nv) : nullptr;
+    g.disp = g.slice(c->disp, np);
+    g.disp1 = c->disp1 ? g.slice(c->disp1, np) : nullptr;
+    g.disp_tmp = c->disp_tmp ? g.slice(c->disp_tmp, np) : nullptr;
+    g.flags = g.slice(c->flags, np);
+    g.flags1 = c->flags1 ? g.slice(c->flags1, np) : nullptr;
+    g.px = g.slice(c->px, 2 * np);
+    g.pxh = g.slice(c->px + (size_t)c->cap * 2 * np, 2 * np);
+    g.pxv = g.slice(c->px + (size_t)2 * c->cap * 2 * np, 2 * np);
+    return g;
 }
+
+// sm_run's group size for n pairs; an asynchronous upload splits its copies by the same figure
+inline int group_size(const sm_ctx* c, int n) { return c->sub_batch > 0 ? c->sub_batch : (c->auto_groups ? (n + 1) / 2 : n); }
 
 // the maps are about to be written: an asynchronous copy of the previous maps must be done
 inline sm_status wait_copy(sm_ctx* c) {
@@ -325,19 +363,23 @@ inline sm_status check_nojoin(sm_ctx* c) {
     return SM_OK;
 }
 
+// Orders the main stream after everything queued on side stream i (one event).  A failed join drains the side
+// stream on the host, so that its groups cannot race later work.
+inline sm_status join_side(sm_ctx* c, int i) {
+    sm_status s = use_event(c, c->ev_join[i]);
+    hipError_t e = s ? hipSuccess : hipEventRecord(c->ev_join[i], c->xst[i]);
+    if (!s && e == hipSuccess) e = hipStreamWaitEvent(c->st, c->ev_join[i], 0);
+    if (e != hipSuccess) s = hip_fail(c, e, "stream join");
+    if (s) hipStreamSynchronize(c->xst[i]);
+    return s;
+}
+
 // A pipelined sm_run leaves its second group running on the side stream; every other entry point
-// first orders the main stream after it (one event), so that it sees (and may overwrite) the state
-// of the whole call.
+// first orders the main stream after it, so that it sees (and may overwrite) the state of the whole call.
 inline sm_status join_all(sm_ctx* c) {
     if (!c->pipe_live) return SM_OK;
     c->pipe_live = false;
-    hipError_t e = hipEventRecord(c->xev[9], c->xst[0]);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->st, c->xev[9], 0);
-    if (e != hipSuccess) {
-        hipStreamSynchronize(c->xst[0]);   // a failed join: drain on the host
-        return hip_fail(c, e, "stream join");
-    }
-    return SM_OK;
+    return join_side(c, 0);
 }
 
 inline sm_status check(sm_ctx* c) {
@@ -368,18 +410,20 @@ bool cbca_div_safe(const sm_params& p, int k);
 sm_status validate(const sm_params& p, std::string& why);
 void build_luts(sm_ctx* c);
 
-// sm_stages.cpp (all asynchronous on c->st)
-sm_status run_prep(sm_ctx* c, int n, const Bufs& B);
+// sm_stages.cpp (all asynchronous on the group's stream)
+sm_status run_prep(sm_ctx* c, const Group& G);
 bool cost_scan_fused(const sm_ctx* c, int view);
-sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B);
-sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B);
-sm_status run_scale(sm_ctx* c, int n, int view, float w, const Bufs& B);
-sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B);
-sm_status run_refine(sm_ctx* c, int n, const Bufs& B);
+sm_status run_cost(sm_ctx* c, int view, const Group& G);
+sm_status run_cbca(sm_ctx* c, int view, bool fuse_scale, float w, const Group& G);
+sm_status run_scale(sm_ctx* c, int view, float w, const Group& G);
+sm_status run_optimize(sm_ctx* c, int view, const Group& G);
+sm_status run_refine(sm_ctx* c, const Group& G);
 
 // sm_stages_agg.cpp
-sm_status run_nl(sm_ctx* c, int n, const Bufs& B, bool solve_all, float w, Bufs* pipe = nullptr, float* out = nullptr);
-sm_status run_other_agg(sm_ctx* c, int n, const Bufs& B, bool solve_all = false, float w = 1.f);
+sm_status nl_open(sm_ctx* c, hipStream_t st);
+Group nl_front(const sm_ctx* c, const Group& G, int set);
+sm_status run_nl(sm_ctx* c, const Group& G, bool solve_all, float w, const Group* front = nullptr, float* out = nullptr);
+sm_status run_other_agg(sm_ctx* c, const Group& G, bool solve_all = false, float w = 1.f);
 bool agg_scale_fused(const sm_params& p, int view);
 const uint16_t* aws_tables();
 sm_status aws_alloc_bands(sm_ctx* c);

@@ -46,22 +46,28 @@ sm_status apply_schedule(sm_ctx* c, int num_streams, int sub_batch) {
     return SM_OK;
 }
 
-sm_status upload(sm_ctx* c, int n, const uint8_t* lbgr, const uint8_t* rbgr, size_t cstride, const uint8_t* lgray,
-                 const uint8_t* rgray, size_t gstride) {
-    const sm_params& p = c->p;
-    const size_t H = p.rows, W = p.cols;
-    // dst rows: pair-major, view-interleaved; src: n stacked images of H rows each
-    const size_t crow = W * 3;
+// Queues the copies of pairs [b0, b1) of both views, colour and gray, on `st`.  dst rows: pair-major,
+// view-interleaved; src: stacked images of p.rows rows each, cstride / gstride bytes per row
+static sm_status copy_images(sm_ctx* c, int b0, int b1, const uint8_t* lbgr, const uint8_t* rbgr, size_t cstride,
+                             const uint8_t* lgray, const uint8_t* rgray, size_t gstride, hipStream_t st) {
+    const size_t H = c->p.rows, W = c->p.cols, crow = W * 3;
     for (int view = 0; view < 2; view++) {
         const uint8_t* src = view == 0 ? lbgr : rbgr;
         const uint8_t* gsrc = view == 0 ? lgray : rgray;
-        for (int b = 0; b < n; b++) {
+        for (int b = b0; b < b1; b++) {
             uint8_t* dst = c->bgr + ((size_t)b * 2 + view) * c->npix * 3;
-            HIP_TRY(c, hipMemcpy2DAsync(dst, crow, src + (size_t)b * H * cstride, cstride, crow, H, hipMemcpyDefault, c->st));
+            HIP_TRY(c, hipMemcpy2DAsync(dst, crow, src + (size_t)b * H * cstride, cstride, crow, H, hipMemcpyDefault, st));
             uint8_t* gdst = c->gray + ((size_t)b * 2 + view) * c->npix;
-            HIP_TRY(c, hipMemcpy2DAsync(gdst, W, gsrc + (size_t)b * H * gstride, gstride, W, H, hipMemcpyDefault, c->st));
+            HIP_TRY(c, hipMemcpy2DAsync(gdst, W, gsrc + (size_t)b * H * gstride, gstride, W, H, hipMemcpyDefault, st));
         }
     }
+    return SM_OK;
+}
+
+sm_status upload(sm_ctx* c, int n, const uint8_t* lbgr, const uint8_t* rbgr, size_t cstride, const uint8_t* lgray,
+                 const uint8_t* rgray, size_t gstride) {
+    sm_status s = copy_images(c, 0, n, lbgr, rbgr, cstride, lgray, rgray, gstride, c->st);
+    if (s) return s;
     HIP_TRY(c, hipStreamSynchronize(c->st));
     c->n_loaded = n;
     c->stage = 1;
@@ -81,6 +87,67 @@ sm_status sm_upload_batch(sm_ctx* c, int32_t n, const uint8_t* lbgr, const uint8
 
 static sm_status place_volumes(sm_ctx* c, int k, int n, float reg_lambda);
 
+// what sm_run decides once per call
+struct Schedule {
+    float w;       // SolveAll's weight
+    bool piped;    // the pipelined two-group form
+    bool early;    // group k + 1 starts after group k's first CBCA sweep (else after its aggregation)
+    bool start;    // the groups start from a joined state
+    bool nl_pipe;  // prep, cost volume and trees on the NL front stream (run_nl)
+};
+
+// Group k of an sm_run: every stage of G's pairs on G's stream, with the events that tie it to the other
+// groups, to the asynchronous map copy and to the next asynchronous upload.
+static sm_status run_group(sm_ctx* c, Group G, int k, const Schedule& S) {
+    const int ns = c->nstreams;
+    sm_status s = SM_OK;
+    if (ns > 1 && k > 0 && S.start) HIP_TRY(c, hipStreamWaitEvent(G.st, c->ev_stagger[(k - 1) % 8], 0));
+    Group Go = G;   // what the optimiser reads
+    const int set = c->nl_set;   // (NL: the record / table set this call's run_nl takes)
+    if (S.nl_pipe) {
+        if ((s = nl_open(c, G.st))) return s;
+        const Group F = nl_front(c, G, set);
+        if ((s = run_nl(c, G, true, S.w, &F))) return s;
+        Go.flags = F.flags;   // the final volume is vm[0]; the penalty flags are the set's
+    } else {
+        if ((s = run_prep(c, G))) return s;
+        if ((s = run_cost(c, 0, G))) return s;
+        if (right_view(c->p) && (s = run_cost(c, 1, G))) return s;
+        if ((s = run_other_agg(c, G, SM_FUSE_SOLVE_ALL, S.w))) return s;   // SolveAll fused into GF / NL
+    }
+    // the group's input images are read by prep and the cost volume only (CBCA + SGM, no refinement:
+    // the pipelined form): the next call's async upload may overwrite them once ev_in[k] is recorded --
+    // here; or, where a fused first CBCA sweep reads the gray images and census codes itself, by run_cbca
+    // after the last view's first sweep
+    if (S.piped && SM_UP_EARLY) {
+        if ((s = use_event(c, c->ev_in[k]))) return s;
+        if (cost_scan_fused(c, 0)) G.in_ev = c->ev_in[k];
+        else HIP_TRY(c, hipEventRecord(c->ev_in[k], G.st));
+    }
+    if (ns > 1 && (s = use_event(c, c->ev_stagger[k % 8]))) return s;
+    if (ns > 1 && S.early) G.stagger_ev = c->ev_stagger[k % 8];   // run_cbca records it after its first sweep
+    for (int v = 0; v < n_views(c->p) && !S.nl_pipe; v++) {
+        if (c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0)
+            s = run_cbca(c, v, true, S.w, G);   // SolveAll fused into the last pass
+        else if (!SM_FUSE_SOLVE_ALL || !agg_scale_fused(c->p, v))
+            s = run_scale(c, v, S.w, G);      // (GF, FIF, AWS, BF, GFNL and NL's vm[0]: fused above)
+        if (s) return s;
+    }
+    // the maps are written from here on: an asynchronous copy of the previous run's maps
+    // (sm_download_disp_async) must be done reading them
+    // (a split copy: ev_copy covers pairs [0, copy_g) only; a group reaching past them -- the
+    // second group, or any group of a different split or schedule -- waits for ev_copy2,
+    // recorded after both copies)
+    const bool past = c->copy_split && G.off + G.n > c->copy_g;
+    if (c->copy_pending) HIP_TRY(c, hipStreamWaitEvent(G.st, past ? c->ev_copy2 : c->ev_copy, 0));
+    if (ns > 1 && !S.early) HIP_TRY(c, hipEventRecord(c->ev_stagger[k % 8], G.st));   // the group's aggregation is done
+    for (int v = 0; v < opt_views(c->p); v++)
+        if ((s = run_optimize(c, v, Go))) return s;
+    if (S.nl_pipe) HIP_TRY(c, hipEventRecord(c->nl_ev_opt[set], G.st));   // the NL set is released
+    if (c->p.do_refine && (s = run_refine(c, G))) return s;
+    return SM_OK;
+}
+
 sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     sm_status s = check_nojoin(c);   // (a pipelined run continues from the previous one's streams)
     if (s) return s;
@@ -92,13 +159,13 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
         if ((s = join_all(c)) || (s = place_volumes(c, k, n, reg_lambda))) return s;
     }
     const float m = 1 + reg_lambda;
-    const float w = (float)(1. / (double)m);
     // Sub-batches: all stages of a group of pairs run back to back so that one pass's output is
     // still in the 256 MB Infinity Cache when the next pass reads it.  With SM_STREAMS = s > 1 the
-    // groups alternate over s streams and group k + 1 starts once group k has finished its CBCA,
-    // so the LDS-bound aggregation sweeps of one group share the CUs with the SGM paths of the
-    // previous one; the main stream joins every stream at the end.
-    const int g = c->sub_batch > 0 ? c->sub_batch : (c->auto_groups ? (n + 1) / 2 : n);
+    // groups alternate over s streams (group k on lane k % s: the main stream, then the side streams) and
+    // group k + 1 starts once group k has finished its CBCA, so the LDS-bound aggregation sweeps of one
+    // group share the CUs with the SGM paths of the previous one; the main stream joins every stream at
+    // the end.
+    const int g = group_size(c, n);
     const int ns = c->nstreams;
     // where group k + 1 starts: with CBCA after group k's first CBCA sweep (the next group's
     // prep, cost and first sweep then share the CUs with this group's LDS-bound NORM_SCAN
@@ -115,103 +182,35 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     // instance's allocations moves both by up to 2 ms (tools/overlap_probe2.py).  Only
     // a pipeline start staggers group 1 (after group 0's CBCA); every other entry point joins
     // first (check -> join_all), and the asynchronous map copy waits for both groups.
-    const bool piped = c->pipelined && ns == 2 && n >= 2 && (n + g - 1) / g == 2;
-    const bool early = !piped && SM_STAGGER_STAGE == 1 && c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0;
+    Schedule S;
+    S.w = (float)(1. / (double)m);
+    S.piped = c->pipelined && ns == 2 && n >= 2 && (n + g - 1) / g == 2;
+    S.early = !S.piped && SM_STAGGER_STAGE == 1 && c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0;
     // (a different split of the pairs would let the groups of two calls share a pair: join first)
-    if ((!piped || g != c->pipe_g) && (s = join_all(c))) return s;
-    const bool start = !(piped && c->pipe_live);   // groups start from a joined state
-    hipStream_t main_st = c->st;
-    int k = 0;
-    sm_status s_out = SM_OK;
-    if (ns > 1 && start) {   // the side streams start after everything queued so far on the main stream
-        HIP_TRY(c, hipEventRecord(c->xev[0], main_st));
-        for (int i = 0; i + 1 < ns; i++) HIP_TRY(c, hipStreamWaitEvent(c->xst[i], c->xev[0], 0));
+    if ((!S.piped || g != c->pipe_g) && (s = join_all(c))) return s;
+    S.start = !(S.piped && c->pipe_live);
+    S.nl_pipe = c->nl_pipe && g >= n && ns == 1 && SM_FUSE_SOLVE_ALL;
+    if (ns > 1 && S.start) {   // the side streams start after everything queued so far on the main stream
+        if ((s = use_event(c, c->ev_start))) return s;
+        HIP_TRY(c, hipEventRecord(c->ev_start, c->st));
+        for (int i = 0; i + 1 < ns; i++) HIP_TRY(c, hipStreamWaitEvent(c->xst[i], c->ev_start, 0));
     }
-    for (int off = 0; off < n; off += g, k++) {
-        const int m2 = n - off < g ? n - off : g;
-        const Bufs B = at(c, off);
-        c->st = (ns > 1 && k % ns) ? c->xst[k % ns - 1] : main_st;
-        hipError_t e = hipSuccess;
-        if (ns > 1 && k > 0 && start && (e = hipStreamWaitEvent(c->st, c->xev[1 + (k - 1) % 8], 0)) != hipSuccess) {
-            s_out = hip_fail(c, e, "hipStreamWaitEvent (group stagger)");
-            break;
-        }
-        Bufs Bo = B;   // what the optimiser reads
-        const bool pipe = c->nl_pipe && m2 == n && ns == 1 && SM_FUSE_SOLVE_ALL;
-        if (pipe) {   // prep, cost volume and trees on the NL front stream (run_nl)
-            if ((s_out = run_nl(c, m2, B, true, w, &Bo))) break;
-        } else {
-            if ((s_out = run_prep(c, m2, B))) break;
-            if ((s_out = run_cost(c, m2, 0, B))) break;
-            if (right_view(c->p) && (s_out = run_cost(c, m2, 1, B))) break;
-            if ((s_out = run_other_agg(c, m2, B, SM_FUSE_SOLVE_ALL, w))) break;   // SolveAll fused into GF / NL
-        }
-        // the group's input images are read by prep and the cost volume only (CBCA + SGM, no
-        // refinement: the pipelined form): the next call's async upload may overwrite them now
-        if (piped && SM_UP_EARLY) {
-            if (!c->ev_in[k] && (e = hipEventCreateWithFlags(&c->ev_in[k], hipEventDisableTiming)) != hipSuccess) {
-                s_out = hip_fail(c, e, "hipEventCreate (inputs read)");
-                break;
-            }
-            // (a fused first CBCA sweep reads the gray images and census codes itself: run_cbca
-            // records the event after the last view's first sweep)
-            if (cost_scan_fused(c, 0)) {
-                c->in_ev = c->ev_in[k];
-            } else if ((e = hipEventRecord(c->ev_in[k], c->st)) != hipSuccess) {
-                s_out = hip_fail(c, e, "hipEventRecord (inputs read)");
-                break;
-            }
-        }
-        if (ns > 1 && early) c->stagger_ev = c->xev[1 + k % 8];
-        for (int v = 0; v < n_views(c->p) && !s_out && !pipe; v++) {
-            if (c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0)
-                s_out = run_cbca(c, m2, v, true, w, B);   // SolveAll fused into the last pass
-            else if (!SM_FUSE_SOLVE_ALL || !agg_scale_fused(c->p, v))
-                s_out = run_scale(c, m2, v, w, B);      // (GF, FIF, AWS, BF, GFNL and NL's vm[0]: fused above)
-        }
-        if (s_out) break;
-        // the maps are written from here on: an asynchronous copy of the previous run's maps
-        // (sm_download_disp_async) must be done reading them
-        // (a split copy: ev_copy covers pairs [0, copy_g) only; a group reaching past them -- the
-        // second group, or any group of a different split or schedule -- waits for ev_copy2,
-        // recorded after both copies)
-        const bool past = c->copy_split && off + m2 > c->copy_g;
-        if (c->copy_pending && (e = hipStreamWaitEvent(c->st, past ? c->ev_copy2 : c->ev_copy, 0)) != hipSuccess) {
-            s_out = hip_fail(c, e, "hipStreamWaitEvent (async map copy)");
-            break;
-        }
-        c->stagger_ev = nullptr;
-        c->in_ev = nullptr;
-        if (ns > 1 && !early && (e = hipEventRecord(c->xev[1 + k % 8], c->st)) != hipSuccess) {
-            s_out = hip_fail(c, e, "hipEventRecord (group CBCA done)");
-            break;
-        }
-        for (int v = 0; v < opt_views(c->p) && !s_out; v++) s_out = run_optimize(c, m2, v, Bo);
-        if (s_out) break;
-        if (pipe && (e = hipEventRecord(c->nl_ev_opt[c->nl_opt_set], c->st)) != hipSuccess) {
-            s_out = hip_fail(c, e, "hipEventRecord (NL set released)");
-            break;
-        }
-        if (c->p.do_refine && (s_out = run_refine(c, m2, B))) break;
+    for (int off = 0, k = 0; off < n && !s; off += g, k++) {
+        const int lane = k % ns;
+        s = run_group(c, at(c, off, std::min(g, n - off), lane ? c->xst[lane - 1] : c->st, lane), k, S);
     }
-    c->st = main_st;
-    c->stagger_ev = nullptr;
-    c->in_ev = nullptr;
-    if (piped && !s_out) {
+    if (S.piped && !s) {
         c->pipe_live = true;   // group 1 stays on the side stream (joined by the next other call)
         c->pipe_g = g;
-    } else if (ns > 1) {   // the join runs on the error path too: nothing stays queued behind the main stream
+    } else {   // the join runs on the error path too: nothing stays queued behind the main stream
         for (int i = 0; i + 1 < ns; i++) {
-            hipError_t e = hipEventRecord(c->xev[9 + i], c->xst[i]);
-            if (e == hipSuccess) e = hipStreamWaitEvent(main_st, c->xev[9 + i], 0);
-            if (e != hipSuccess) {
-                // a failed join: drain the side stream on the host so its groups cannot race later work
-                hipStreamSynchronize(c->xst[i]);
-                if (!s_out) s_out = hip_fail(c, e, "stream join");
-            }
+            const std::string why = c->err;
+            const sm_status j = join_side(c, i);
+            if (s) c->err = why;   // (the first failure is the one reported)
+            else s = j;
         }
     }
-    if (s_out) return s_out;
+    if (s) return s;
     c->stage = c->p.do_refine ? 5 : 4;
     c->rx_vol_ok = true;
     if (disp_out) return sm_download_disp(c, n, disp_out);
@@ -300,9 +299,8 @@ sm_status sm_download_disp_async(sm_ctx* c, int32_t n, int16_t* disp_out) {
     if (!disp_out || n < 1 || n > c->cap) return fail(c, SM_EINVAL, "bad arguments");
     if (c->stage < 4) return fail(c, SM_ESTATE, "no disparity map yet");
     if (!c->cst) HIP_TRY(c, hipStreamCreateWithFlags(&c->cst, hipStreamNonBlocking));
-    if (!c->ev_run) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_run, hipEventDisableTiming));
-    if (!c->ev_copy) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
-    if (!c->ev_copy2) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_copy2, hipEventDisableTiming));
+    for (hipEvent_t* ev : {&c->ev_run, &c->ev_copy, &c->ev_copy2, &c->ev_side})
+        if ((s = use_event(c, *ev))) return s;
     HIP_TRY(c, hipEventRecord(c->ev_run, c->st));
     HIP_TRY(c, hipStreamWaitEvent(c->cst, c->ev_run, 0));
     c->copy_split = c->pipe_live && n > c->pipe_g;
@@ -314,22 +312,22 @@ sm_status sm_download_disp_async(sm_ctx* c, int32_t n, int16_t* disp_out) {
         const size_t g = (size_t)c->pipe_g;
         HIP_TRY(c, hipMemcpyAsync(disp_out, c->disp, g * c->npix * 2, hipMemcpyDefault, c->cst));
         HIP_TRY(c, hipEventRecord(c->ev_copy, c->cst));
-        HIP_TRY(c, hipEventRecord(c->xev[10], c->xst[0]));
-        HIP_TRY(c, hipStreamWaitEvent(c->cst, c->xev[10], 0));
+        HIP_TRY(c, hipEventRecord(c->ev_side, c->xst[0]));
+        HIP_TRY(c, hipStreamWaitEvent(c->cst, c->ev_side, 0));
         HIP_TRY(c, hipMemcpyAsync(disp_out + g * c->npix, c->disp + g * c->npix, ((size_t)n - g) * c->npix * 2,
                                   hipMemcpyDefault, c->cst));
         HIP_TRY(c, hipEventRecord(c->ev_copy2, c->cst));
     } else {
         if (c->pipe_live) {   // (n within the first group: its maps only)
-            HIP_TRY(c, hipEventRecord(c->xev[10], c->xst[0]));
-            HIP_TRY(c, hipStreamWaitEvent(c->cst, c->xev[10], 0));
+            HIP_TRY(c, hipEventRecord(c->ev_side, c->xst[0]));
+            HIP_TRY(c, hipStreamWaitEvent(c->cst, c->ev_side, 0));
         }
         HIP_TRY(c, hipMemcpyAsync(disp_out, c->disp, (size_t)n * c->npix * 2, hipMemcpyDefault, c->cst));
         HIP_TRY(c, hipEventRecord(c->ev_copy, c->cst));
     }
     c->copy_pending = true;
     // (one event after both copies on the copy stream: sm_download_wait's per-call marker)
-    if (!c->ev_dl[c->dl_slot]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_dl[c->dl_slot], hipEventDisableTiming));
+    if ((s = use_event(c, c->ev_dl[c->dl_slot]))) return s;
     HIP_TRY(c, hipEventRecord(c->ev_dl[c->dl_slot], c->cst));
     c->dl_slot ^= 1;
     c->dl_count++;
@@ -357,41 +355,30 @@ sm_status sm_upload_batch_async(sm_ctx* c, int32_t n, const uint8_t* lbgr, const
     if (s) return s;
     if (n < 1 || n > c->cap) return fail(c, SM_EINVAL, "n must be in [1, batch_capacity]");
     if (!lbgr || !rbgr || !lgray || !rgray) return fail(c, SM_EINVAL, "null image pointer");
-    // the split the next run will keep (sm_run: g = (n + 1) / 2 under the auto schedule); any
-    // other shape joins first, as a synchronous upload does
-    const int g = c->sub_batch > 0 ? c->sub_batch : (c->auto_groups ? (n + 1) / 2 : n);
+    // the split the next run will keep (group_size); any other shape joins first, as a synchronous
+    // upload does
+    const int g = group_size(c, n);
     const bool split = c->pipe_live && c->pipelined && g == c->pipe_g && (n + g - 1) / g == 2;
     if (!split && (s = join_all(c))) return s;
     for (int i = 0; i < 2; i++)
-        if (!c->ev_up[i]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_up[i], hipEventDisableTiming));
-    const sm_params& p = c->p;
-    const size_t H = p.rows, W = p.cols, crow = W * 3;
+        if ((s = use_event(c, c->ev_up[i]))) return s;
+    const size_t crow = (size_t)c->p.cols * 3, grow = (size_t)c->p.cols;
+    auto copy = [&](int b0, int b1, hipStream_t st) { return copy_images(c, b0, b1, lbgr, rbgr, crow, lgray, rgray, grow, st); };
     // early: the copies go on their own stream as soon as each group's previous inputs are read
     // (ev_in, recorded after its cost volume -- after its first CBCA sweep where that sweep computes
     // the costs from the gray images itself, run_cbca), so they overlap that group's CBCA and SGM; the
     // group's next kernels wait for its copies (ev_up)
     const bool early = split && SM_UP_EARLY && c->ev_in[0] && c->ev_in[1];
     const hipStream_t ust = nullptr;
-    for (int grp = 0; grp < (early ? 2 : 1); grp++) {
-        if (early) HIP_TRY(c, hipStreamWaitEvent(ust, c->ev_in[grp], 0));
-        const int b0 = early ? grp * g : 0, b1 = early ? std::min(n, (grp + 1) * g) : n;
-    for (int view = 0; view < 2; view++) {
-        const uint8_t* src = view == 0 ? lbgr : rbgr;
-        const uint8_t* gsrc = view == 0 ? lgray : rgray;
-        for (int b = b0; b < b1; b++) {
-            hipStream_t st = early ? ust : (split && b >= g) ? c->xst[0] : c->st;
-            uint8_t* dst = c->bgr + ((size_t)b * 2 + view) * c->npix * 3;
-            HIP_TRY(c, hipMemcpy2DAsync(dst, crow, src + (size_t)b * H * crow, crow, crow, H, hipMemcpyDefault, st));
-            uint8_t* gdst = c->gray + ((size_t)b * 2 + view) * c->npix;
-            HIP_TRY(c, hipMemcpy2DAsync(gdst, W, gsrc + (size_t)b * H * W, W, W, H, hipMemcpyDefault, st));
-        }
+    for (int grp = 0; early && grp < 2; grp++) {
+        HIP_TRY(c, hipStreamWaitEvent(ust, c->ev_in[grp], 0));
+        if ((s = copy(grp * g, std::min(n, (grp + 1) * g), ust))) return s;
+        HIP_TRY(c, hipEventRecord(c->ev_up[grp], ust));
+        HIP_TRY(c, hipStreamWaitEvent(grp == 0 ? c->st : c->xst[0], c->ev_up[grp], 0));
     }
-        if (early) {
-            HIP_TRY(c, hipEventRecord(c->ev_up[grp], ust));
-            HIP_TRY(c, hipStreamWaitEvent(grp == 0 ? c->st : c->xst[0], c->ev_up[grp], 0));
-        }
-    }
-    if (!early) {
+    if (!early) {   // each group's pairs on the group's own stream
+        if ((s = copy(0, split ? g : n, c->st))) return s;
+        if (split && (s = copy(g, n, c->xst[0]))) return s;
         HIP_TRY(c, hipEventRecord(c->ev_up[0], c->st));
         if (split) HIP_TRY(c, hipEventRecord(c->ev_up[1], c->xst[0]));
     }

@@ -1,6 +1,7 @@
 // sm_stages.cpp — the stage drivers of the default pipeline: each fills a kernel family's argument struct from
-// the context and queues its launches on c->st (prep, cost volume, CBCA in its three forms, SolveAll's scale,
-// dispOptimize with Do_vmTop, refine).  The other aggregations' drivers are in sm_stages_agg.cpp.
+// the context and the group descriptor it is given and queues its launches on the group's stream (prep, cost
+// volume, CBCA in its three forms, SolveAll's scale, dispOptimize with Do_vmTop, refine).  The other aggregations'
+// drivers are in sm_stages_agg.cpp.
 #include <math.h>
 
 #include <cmath>
@@ -8,17 +9,17 @@
 #include "sm_ctx.h"
 
 // what both prep passes of run_prep share: the group's planes, the census window and window 0's arm settings
-static sm::PrepArgs prep_args(const sm_ctx* c, const Bufs& B) {
+static sm::PrepArgs prep_args(const sm_ctx* c, const Group& G) {
     const sm_params& p = c->p;
     sm::PrepArgs a{};
-    a.gray = B.gray;
-    a.bgr = B.bgr;
-    a.px = B.px;
-    a.pxh = B.pxh;
-    a.pxv = B.pxv;
-    a.code = B.code;
-    a.arms = B.arms;
-    a.flags = B.flags;
+    a.gray = G.gray;
+    a.bgr = G.bgr;
+    a.px = G.px;
+    a.pxh = G.pxh;
+    a.pxv = G.pxv;
+    a.code = G.code;
+    a.arms = G.arms;
+    a.flags = G.flags;
     a.H = p.rows;
     a.W = p.cols;
     a.rv = p.census_rv;
@@ -33,34 +34,34 @@ static sm::PrepArgs prep_args(const sm_ctx* c, const Bufs& B) {
     return a;
 }
 
-sm_status run_prep(sm_ctx* c, int n, const Bufs& B) {
+sm_status run_prep(sm_ctx* c, const Group& G) {
     const sm_params& p = c->p;
     const bool census = needs_census(p), arms = needs_arms(p);
     const bool flags = p.optimization == SM_OPT_SGM;
     if (c->dw_on) {
         // window 1's arms first (calArms with cbca_crossL[1] .., cpp:4343), through the same arm kernels into
         // their own planes; the pass below then leaves the arm-walk planes as window 0 wrote them
-        sm::PrepArgs a = prep_args(c, B);
-        a.arms = c->arms2 + (size_t)(B.arms - c->arms);
+        sm::PrepArgs a = prep_args(c, G);
+        a.arms = G.slice(c->arms2, 2 * 2 * c->npix * 4);
         a.L = c->dw_l;
         a.L_out = c->dw_l_out;
         a.C_D = c->dw_ct;
         a.C_D_out = c->dw_ct_out;
         a.do_arms = 1;
-        sm_status s = timed(c, "prep_dw", (double)n * 2 * c->npix * (3 + 8), [&] { sm::launch_prep(a, n, c->st); });
+        sm_status s = timed(c, G.st, "prep_dw", (double)G.n * 2 * c->npix * (3 + 8), [&] { sm::launch_prep(a, G.n, G.st); });
         if (s) return s;
     }
     {
-        sm::PrepArgs a = prep_args(c, B);
-        a.flags1 = flags && p.do_refine ? B.flags1 : nullptr;
+        sm::PrepArgs a = prep_args(c, G);
+        a.flags1 = flags && p.do_refine ? G.flags1 : nullptr;
         a.do_census = census;
         a.do_arms = arms;
         a.do_flags = flags;
         // the packed BGR plane's later readers: the GF image planes, so, refine's properIpol
         a.pack_px = uses_gf(p) || p.optimization == SM_OPT_SO || p.do_refine;
-        return timed(c, "prep", (double)n * 2 * c->npix * (1 + 3 + (census ? 16 : 0) + (arms ? 8 : 0)) +
-                                    (flags ? (double)n * c->npix * n_views(p) : 0),
-                     [&] { sm::launch_prep(a, n, c->st); });
+        return timed(c, G.st, "prep", (double)G.n * 2 * c->npix * (1 + 3 + (census ? 16 : 0) + (arms ? 8 : 0)) +
+                                    (flags ? (double)G.n * c->npix * n_views(p) : 0),
+                     [&] { sm::launch_prep(a, G.n, G.st); });
     }
 }
 
@@ -79,15 +80,15 @@ bool cost_scan_fused(const sm_ctx* c, int view) {
            sm::cbca_hsc_smem_bytes(lag, cw) <= 64 * 1024;
 }
 
-sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
+sm_status run_cost(sm_ctx* c, int view, const Group& G) {
     const sm_params& p = c->p;
     if (cost_scan_fused(c, view)) return SM_OK;
     sm::CostArgs a{};
-    a.vm = view == 0 ? B.vm0 : B.vm1;
-    a.code = B.code;
-    a.gray = B.gray;
-    a.arms = B.arms;
-    a.bgr = B.bgr;
+    a.vm = G.vm(view);
+    a.code = G.code;
+    a.gray = G.gray;
+    a.arms = G.arms;
+    a.bgr = G.bgr;
     a.H = p.rows;
     a.W = p.cols;
     a.D = p.num_disparities;
@@ -114,15 +115,15 @@ sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
         }
         a.grad_oor = (float)sqrt(pow((double)a.grad_trunc, 2) * 2);
         const int m = p.cost_method;   // sm::SM_M_SD .. carry sm_cost_method's values
-        return timed(c, view == 0 ? "cost_volume" : "cost_volume_right", (double)n * c->nvol * 4.0,
-                     [&] { sm::launch_cost_ext(a, m, n, c->st); });
+        return timed(c, G.st, view == 0 ? "cost_volume" : "cost_volume_right", (double)G.n * c->nvol * 4.0,
+                     [&] { sm::launch_cost_ext(a, m, G.n, G.st); });
     }
     const int m = p.cost_method == SM_COST_CENSUS_GRAD ? sm::SM_M_CENSUS_GRAD
                   : p.cost_method == SM_COST_CENSUS    ? sm::SM_M_CENSUS
                   : p.cost_method == SM_COST_AD_CENSUS ? sm::SM_M_AD_CENSUS
                                                        : sm::SM_M_AD;
-    return timed(c, view == 0 ? "cost_volume" : "cost_volume_right", (double)n * c->nvol * 4.0,
-                 [&] { sm::launch_cost(a, m, n, c->st); });
+    return timed(c, G.st, view == 0 ? "cost_volume" : "cost_volume_right", (double)G.n * c->nvol * 4.0,
+                 [&] { sm::launch_cost(a, m, G.n, G.st); });
 }
 
 // cbca_core with cbca_intersect == false (cpp:5585-5666) on a view: the arms of the view's own image, one area per
@@ -131,15 +132,14 @@ sm_status run_cost(sm_ctx* c, int n, int view, const Bufs& B) {
 // its second window kernel divides by the area and, in the last iteration of sm_run, applies SolveAll's weight
 // (scaling an element commutes with nothing else after the division).  The areas ping-pong between the two
 // planes the same way and end in plane 0.
-static sm_status run_cbca_ni(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B, int win) {
+static sm_status run_cbca_ni(sm_ctx* c, int view, bool fuse_scale, float w, const Group& G, int win) {
     const sm_params& p = c->p;
     const int N = cbca_iters(c);
-    const size_t pair_off = (size_t)(B.vm0 - c->vm0);
-    float* vol = win ? c->vm2 + pair_off : (view == 0 ? B.vm0 : B.vm1);
-    float* tmp = c->ni_tmp + pair_off;
+    float* vol = win ? G.slice(c->vm2, c->nvol) : G.vm(view);
+    float* tmp = G.slice(c->ni_tmp, c->nvol);
     sm::NiArgs a{};
-    a.arms = (const uint32_t*)(win ? c->arms2 + (size_t)(B.arms - c->arms) : B.arms);
-    a.area = c->ni_area + pair_off / c->nvol * 4 * c->npix;
+    a.arms = (const uint32_t*)(win ? G.slice(c->arms2, 2 * 2 * c->npix * 4) : G.arms);
+    a.area = G.slice(c->ni_area, 4 * c->npix);
     a.H = p.rows;
     a.W = p.cols;
     a.D = p.num_disparities;
@@ -147,8 +147,8 @@ static sm_status run_cbca_ni(sm_ctx* c, int n, int view, bool fuse_scale, float 
     a.scale = w;
     // algorithmic bytes: the prefix reads and writes the volume; the window reads every prefix position once
     // from memory (it is the head of one pixel and the tail of another) and writes the other volume
-    const double bytes = (double)n * c->nvol * 8.0;
-    const std::string sfx = std::string(view == 0 ? "" : "_r") + (win ? "_dw" : "") + "_ni";
+    const double bytes = (double)G.n * c->nvol * 8.0;
+    const std::string sfx = Group::name("", view) + (win ? "_dw" : "") + "_ni";
     sm_status s;
     for (int k = 0; k < N; k++) {
         for (int pass = 0; pass < 2; pass++) {
@@ -160,14 +160,12 @@ static sm_status run_cbca_ni(sm_ctx* c, int n, int view, bool fuse_scale, float 
             a.norm = pass == 1;
             a.apply_scale = fuse_scale && pass == 1 && k + 1 == N ? 1 : 0;
             const std::string dir = a.horiz ? "cbca_h_" : "cbca_v_";
-            if ((s = timed(c, (dir + "prefix" + sfx).c_str(), bytes, [&] { sm::launch_ni_prefix(a, n, c->st); }))) return s;
-            if ((s = timed(c, (dir + (a.norm ? "window_norm" : "window") + sfx).c_str(), bytes,
-                           [&] { sm::launch_ni_window(a, n, c->st); })))
+            if ((s = timed(c, G.st, (dir + "prefix" + sfx).c_str(), bytes, [&] { sm::launch_ni_prefix(a, G.n, G.st); }))) return s;
+            if ((s = timed(c, G.st, (dir + (a.norm ? "window_norm" : "window") + sfx).c_str(), bytes,
+                           [&] { sm::launch_ni_window(a, G.n, G.st); })))
                 return s;
-            if (!win && c->stagger_ev) {   // the next group may start (as after the intersecting form's first sweep)
-                HIP_TRY(c, hipEventRecord(c->stagger_ev, c->st));
-                c->stagger_ev = nullptr;
-            }
+            // the next group may start (as after the intersecting form's first sweep)
+            if (!win && view == 0 && k == 0 && pass == 0 && G.stagger_ev) HIP_TRY(c, hipEventRecord(G.stagger_ev, G.st));
         }
     }
     c->ni_ran = true;
@@ -178,20 +176,19 @@ static sm_status run_cbca_ni(sm_ctx* c, int n, int view, bool fuse_scale, float 
 // double window).  win 1: the double window's large-window run, on the second volume with window 1's arms,
 // lag and ring size; it records none of the group's events (the window-0 run that follows reads the same
 // inputs last).
-static sm_status run_cbca_core(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B, int win) {
+static sm_status run_cbca_core(sm_ctx* c, int view, bool fuse_scale, float w, const Group& G, int win) {
     // cbca_core (cpp:5585-5666): iteration k runs H then V for even k, V then H for odd k.
     // The last pass of iteration k and the first pass of iteration k+1 share a direction and
     // are fused into one CB_NORM_SCAN sweep, so N iterations take N + 1 sweeps.
     const sm_params& p = c->p;
     const int N = cbca_iters(c);
     if (N <= 0) return SM_OK;
-    if (c->ni_on) return run_cbca_ni(c, n, view, fuse_scale, w, B, win);
-    const size_t pair_off = (size_t)(B.vm0 - c->vm0);   // floats from the allocation base to the group's first pair
+    if (c->ni_on) return run_cbca_ni(c, view, fuse_scale, w, G, win);
     sm::CbcaArgs a{};
-    a.vm = win ? c->vm2 + pair_off : (view == 0 ? B.vm0 : B.vm1);
+    a.vm = win ? G.slice(c->vm2, c->nvol) : G.vm(view);
     a.view = view;
     a.dummy = c->dummy;
-    a.arms = (const uint32_t*)(win ? c->arms2 + (size_t)(B.arms - c->arms) : B.arms);
+    a.arms = (const uint32_t*)(win ? G.slice(c->arms2, 2 * 2 * c->npix * 4) : G.arms);
     a.H = p.rows;
     a.W = p.cols;
     a.D = p.num_disparities;
@@ -202,50 +199,45 @@ static sm_status run_cbca_core(sm_ctx* c, int n, int view, bool fuse_scale, floa
     a.apply_scale = 0;
     a.num_cu = c->num_cu;
     a.arm_pad_rows = 2 * a.lag;
-    const double bytes = (double)n * c->nvol * 8.0;
+    const double bytes = (double)G.n * c->nvol * 8.0;
     // profile names: "cbca_h_scan" etc. for vm[0], "cbca_h_scan_r" etc. for vm[1]; "_dw" for the large window
-    std::string sfx = std::string(view == 0 ? "" : "_r") + (win ? "_dw" : "");
-    auto nm = [&](const char* base) { return std::string(base) + sfx; };
+    auto nm = [&](const char* base) { return Group::name(base, view) + (win ? "_dw" : ""); };
     sm_status s;
     if (cost_scan_fused(c, view)) {   // the costs are computed in the sweep: it only writes the volume
-        a.code = B.code;
-        a.gray = B.gray;
+        a.code = G.code;
+        a.gray = G.gray;
         a.lut = c->luts;
         a.census_default = (float)census_len(p) * 1.0f;
         a.grad_trunc = p.grad_trunc;
         a.grad_adaptive = p.grad_adaptive;
         a.cwords = (census_len(p) + 31) / 32;
         // grad() built its adaptive weights from window 0's arms (cpp:630-633), before CBCA() made window 1's
-        a.cost_arms = win ? (const uint32_t*)B.arms : nullptr;
-        s = timed(c, nm("cbca_h_scan_cost"), (double)n * c->nvol * 4.0, [&] { sm::launch_cbca_hsc(a, n, c->st); });
+        a.cost_arms = win ? (const uint32_t*)G.arms : nullptr;
+        s = timed(c, G.st, nm("cbca_h_scan_cost"), (double)G.n * c->nvol * 4.0, [&] { sm::launch_cbca_hsc(a, G.n, G.st); });
     } else {
-        s = timed(c, nm("cbca_h_scan"), bytes, [&] { sm::launch_cbca(a, true, sm::CB_SCAN, n, c->st); });
+        s = timed(c, G.st, nm("cbca_h_scan"), bytes, [&] { sm::launch_cbca(a, true, sm::CB_SCAN, G.n, G.st); });
     }
     if (s) return s;
-    if (!win && c->in_ev && view == n_views(p) - 1) {   // the last sweep that reads the group's input images
-        HIP_TRY(c, hipEventRecord(c->in_ev, c->st));
-        c->in_ev = nullptr;
-    }
-    if (!win && c->stagger_ev) {   // the next group may start: this group's next sweep is LDS- and issue-bound
-        HIP_TRY(c, hipEventRecord(c->stagger_ev, c->st));
-        c->stagger_ev = nullptr;
-    }
+    // the last sweep that reads the group's input images
+    if (!win && view == n_views(p) - 1 && G.in_ev) HIP_TRY(c, hipEventRecord(G.in_ev, G.st));
+    // the next group may start: this group's next sweep is LDS- and issue-bound
+    if (!win && view == 0 && G.stagger_ev) HIP_TRY(c, hipEventRecord(G.stagger_ev, G.st));
     for (int k = 0; k < N; k++) {
         const bool dir_h = (k % 2 == 1);  // direction of iteration k's second pass
         a.div_safe = cbca_div_safe(p, k) ? 1 : 0;   // this step's normalisation is iteration k's
         if (k + 1 < N && c->fuse_norm_scan) {
-            s = timed(c, nm(dir_h ? "cbca_h_norm_scan" : "cbca_v_norm_scan"), bytes,
-                      [&] { sm::launch_cbca(a, dir_h, sm::CB_NORM_SCAN, n, c->st); });
+            s = timed(c, G.st, nm(dir_h ? "cbca_h_norm_scan" : "cbca_v_norm_scan"), bytes,
+                      [&] { sm::launch_cbca(a, dir_h, sm::CB_NORM_SCAN, G.n, G.st); });
         } else if (k + 1 < N) {
-            s = timed(c, nm(dir_h ? "cbca_h_norm" : "cbca_v_norm"), bytes,
-                      [&] { sm::launch_cbca(a, dir_h, sm::CB_NORM, n, c->st); });
+            s = timed(c, G.st, nm(dir_h ? "cbca_h_norm" : "cbca_v_norm"), bytes,
+                      [&] { sm::launch_cbca(a, dir_h, sm::CB_NORM, G.n, G.st); });
             if (s) return s;
-            s = timed(c, nm(dir_h ? "cbca_h_scan" : "cbca_v_scan"), bytes,
-                      [&] { sm::launch_cbca(a, dir_h, sm::CB_SCAN, n, c->st); });
+            s = timed(c, G.st, nm(dir_h ? "cbca_h_scan" : "cbca_v_scan"), bytes,
+                      [&] { sm::launch_cbca(a, dir_h, sm::CB_SCAN, G.n, G.st); });
         } else {
             a.apply_scale = fuse_scale ? 1 : 0;
-            s = timed(c, nm(dir_h ? "cbca_h_norm" : "cbca_v_norm"), bytes,
-                      [&] { sm::launch_cbca(a, dir_h, sm::CB_NORM, n, c->st); });
+            s = timed(c, G.st, nm(dir_h ? "cbca_h_norm" : "cbca_v_norm"), bytes,
+                      [&] { sm::launch_cbca(a, dir_h, sm::CB_NORM, G.n, G.st); });
         }
         if (s) return s;
     }
@@ -259,96 +251,92 @@ static sm_status run_cbca_core(sm_ctx* c, int n, int view, bool fuse_scale, floa
 // once, with view 0) and the selection.  SolveAll's weight is fused into the last normalising pass of both
 // runs: every element of the composed volume is one of the two runs' elements, and scaling an element commutes
 // with choosing it, so the result equals "compose, then scale" bit for bit.
-sm_status run_cbca(sm_ctx* c, int n, int view, bool fuse_scale, float w, const Bufs& B) {
-    if (!c->dw_on) return run_cbca_core(c, n, view, fuse_scale, w, B, 0);
+sm_status run_cbca(sm_ctx* c, int view, bool fuse_scale, float w, const Group& G) {
+    if (!c->dw_on) return run_cbca_core(c, view, fuse_scale, w, G, 0);
     const sm_params& p = c->p;
-    const size_t pair_off = (size_t)(B.vm0 - c->vm0);
     sm_status s;
     if (!cost_scan_fused(c, view)) {
-        const float* raw = view == 0 ? B.vm0 : B.vm1;
-        float* dst = c->vm2 + pair_off;
-        const size_t bytes = (size_t)n * c->nvol * 4;
+        const float* raw = G.vm(view);
+        float* dst = G.slice(c->vm2, c->nvol);
+        const size_t bytes = (size_t)G.n * c->nvol * 4;
         hipError_t e = hipSuccess;
-        s = timed(c, view == 0 ? "dw_copy_raw" : "dw_copy_raw_r", 2.0 * bytes,
-                  [&] { e = hipMemcpyAsync(dst, raw, bytes, hipMemcpyDeviceToDevice, c->st); });
+        s = timed(c, G.st, Group::name("dw_copy_raw", view), 2.0 * bytes,
+                  [&] { e = hipMemcpyAsync(dst, raw, bytes, hipMemcpyDeviceToDevice, G.st); });
         if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync (raw costs for the large window)");
         if (s) return s;
     }
-    if ((s = run_cbca_core(c, n, view, fuse_scale, w, B, 1))) return s;
-    if ((s = run_cbca_core(c, n, view, fuse_scale, w, B, 0))) return s;
+    if ((s = run_cbca_core(c, view, fuse_scale, w, G, 1))) return s;
+    if ((s = run_cbca_core(c, view, fuse_scale, w, G, 0))) return s;
     sm::DwArgs a{};
-    a.arms = (const uint32_t*)B.arms;
+    a.arms = (const uint32_t*)G.arms;
     a.mask = c->dw_mask;
     a.vm = view == 0 ? c->vm0 : c->vm1;
     a.vm2 = c->vm2;
-    a.pix0 = pair_off / (size_t)p.num_disparities;
+    a.pix0 = (size_t)G.off * c->npix;
     a.H = p.rows;
     a.W = p.cols;
     a.D = p.num_disparities;
     a.isum = c->dw_isum;
     if (view == 0) {
-        if ((s = timed(c, "dw_mask", (double)n * c->npix * 9.0, [&] { sm::launch_dw_mask(a, n, c->st); }))) return s;
+        if ((s = timed(c, G.st, "dw_mask", (double)G.n * c->npix * 9.0, [&] { sm::launch_dw_mask(a, G.n, G.st); }))) return s;
         c->dw_ran = true;
     }
     // (algorithmic bytes: the mask; the volume traffic is 8 B per selected element, known only from the mask)
-    return timed(c, view == 0 ? "dw_select" : "dw_select_r", (double)n * c->npix, [&] { sm::launch_dw_select(a, n, c->st); });
+    return timed(c, G.st, Group::name("dw_select", view), (double)G.n * c->npix, [&] { sm::launch_dw_select(a, G.n, G.st); });
 }
 
-sm_status run_scale(sm_ctx* c, int n, int view, float w, const Bufs& B) {
-    return timed(c, view == 0 ? "solve_all_scale" : "solve_all_scale_r", (double)n * c->nvol * 8.0,
-                 [&] { sm::launch_scale(view == 0 ? B.vm0 : B.vm1, (size_t)n * c->nvol, w, c->st); });
+sm_status run_scale(sm_ctx* c, int view, float w, const Group& G) {
+    return timed(c, G.st, Group::name("solve_all_scale", view), (double)G.n * c->nvol * 8.0,
+                 [&] { sm::launch_scale(G.vm(view), (size_t)G.n * c->nvol, w, G.st); });
 }
 
 // Do_vmTop (cpp:1111-1121): selectTopCostFromVolumn on vm[view] as the optimiser left it, then
 // genDispFromTopCostVm2 into DP[view]; I_c[0] is the colour image for both views
-static sm_status run_vmtop(sm_ctx* c, int n, int view, const Bufs& B, const float* vm, int16_t* disp) {
+static sm_status run_vmtop(sm_ctx* c, int view, const Group& G, const float* vm, int16_t* disp) {
     const sm_params& p = c->p;
-    const size_t off = (size_t)(B.disp - c->disp) / c->npix;   // the group's first pair
     const size_t T = (size_t)p.cols + 2 * (size_t)p.rows;
-    const char* sfx = view == 0 ? "" : "_r";
     sm::VmTopArgs a{};
     a.vm = vm;
-    a.tab = c->vt_tab + ((size_t)view * c->cap + off) * c->npix * c->vt_num;
-    a.cnt = c->vt_cnt + ((size_t)view * c->cap + off) * c->npix;
-    a.tcnt = c->vt_tcnt + off * T;
-    a.bgr = B.bgr;
+    a.tab = G.slice(c->vt_tab + (size_t)view * c->cap * c->npix * c->vt_num, c->npix * c->vt_num);
+    a.cnt = G.slice(c->vt_cnt + (size_t)view * c->cap * c->npix, c->npix);
+    a.tcnt = G.slice(c->vt_tcnt, T);
+    a.bgr = G.bgr;
     a.disp = disp;
     a.H = p.rows;
     a.W = p.cols;
     a.D = p.num_disparities;
     a.M = c->vt_num;
-    a.n = n;
+    a.n = G.n;
     a.thres = c->vt_thres;
     a.method = c->vt_method;
     a.ts = c->vt_ts;
     a.has_cir2 = c->vt_cir2;
     a.color_limit = c->vt_color;
-    const double np = (double)n * c->npix, tab = 8.0 * a.M + 4;
-    sm_status s = timed(c, (std::string("vmtop_select") + sfx).c_str(), (double)n * c->nvol * 4.0 + np * tab,
-                        [&] { sm::launch_vmtop_select(a, c->st); });
+    const double np = (double)G.n * c->npix, tab = 8.0 * a.M + 4;
+    sm_status s = timed(c, G.st, Group::name("vmtop_select", view), (double)G.n * c->nvol * 4.0 + np * tab,
+                        [&] { sm::launch_vmtop_select(a, G.st); });
     if (s) return s;
     c->vt_ran_num[view] = a.M;
     if (a.method == 0) {
-        HIP_TRY(c, hipMemsetAsync(a.tcnt, 0, (size_t)n * T * sizeof(int), c->st));
-        if ((s = timed(c, (std::string("vmtop_decide0_a") + sfx).c_str(), np * (9 * tab + 2),
-                       [&] { sm::launch_vmtop_decide0_a(a, c->st); })))
+        HIP_TRY(c, hipMemsetAsync(a.tcnt, 0, (size_t)G.n * T * sizeof(int), G.st));
+        if ((s = timed(c, G.st, Group::name("vmtop_decide0_a", view), np * (9 * tab + 2),
+                       [&] { sm::launch_vmtop_decide0_a(a, G.st); })))
             return s;
         for (int r = 0; r < sm::VMTOP_RELAX_ROUNDS; r++)
-            if ((s = timed(c, (std::string("vmtop_decide0_w") + sfx).c_str(), np * 2, [&] { sm::launch_vmtop_decide0_w(a, c->st); })))
+            if ((s = timed(c, G.st, Group::name("vmtop_decide0_w", view), np * 2, [&] { sm::launch_vmtop_decide0_w(a, G.st); })))
                 return s;
-        return timed(c, (std::string("vmtop_decide0_b") + sfx).c_str(), (double)n * T * 4 + np * 2,
-                     [&] { sm::launch_vmtop_decide0_b(a, c->st); });
+        return timed(c, G.st, Group::name("vmtop_decide0_b", view), (double)G.n * T * 4 + np * 2,
+                     [&] { sm::launch_vmtop_decide0_b(a, G.st); });
     }
-    return timed(c, (std::string("vmtop_decide12") + sfx).c_str(), np * (tab + 2), [&] { sm::launch_vmtop_decide12(a, c->st); });
+    return timed(c, G.st, Group::name("vmtop_decide12", view), np * (tab + 2), [&] { sm::launch_vmtop_decide12(a, G.st); });
 }
 
 // dispOptimize (cpp:1046-1136) for one view: vm[0] with the left image's penalty flags
 // (leftFirst = true) -> DP[0]; vm[1] with the right image's (leftFirst = false) -> DP[1].
-sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
+sm_status run_optimize(sm_ctx* c, int view, const Group& G) {
     const sm_params& p = c->p;
-    float* vm = view == 0 ? B.vm0 : B.vm1;
-    int16_t* disp = view == 0 ? B.disp : B.disp1;
-    const char* sfx = view == 0 ? "" : "_r";
+    float* vm = G.vm(view);
+    int16_t* disp = G.map(view);
     // Do_vmTop replaces gen_dispFromVm after "sgm" and "" (cpp:1108-1128); "so" never reaches it.  SGM then
     // writes its path sum into vm[view] (the keep_final_volume path) for the selection to read
     const bool vmtop = c->vt_on && p.optimization != SM_OPT_SO;
@@ -360,11 +348,11 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
         static const char* NAMES[8] = {"sgm_path0", "sgm_path1", "sgm_path2", "sgm_path3",
                                        "sgm_path4", "sgm_path5", "sgm_path6", "sgm_path7"};
         sm::SgmArgs a{};
-        a.flags = view == 0 ? B.flags : B.flags1;
+        a.flags = G.penalty(view);
         a.dummy = c->dummy;
         a.vm = vm;
-        a.acc = B.acc;
-        a.bgr = B.bgr;
+        a.acc = G.acc;
+        a.bgr = G.bgr;
         a.disp = disp;
         a.H = p.rows;
         a.W = p.cols;
@@ -380,13 +368,13 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
         // BF's are >= +0 while its sums are exact (bf_exact)
         a.signed_costs = uses_gf(p) || (p.aggregation == SM_AGG_BF && !bf_exact(p));
         int first = 0;   // first path left to the plain sweeps
-        if (B.ck) {
+        if (G.ck) {
             // checkpointed pairs (0, 1) and (2, 3): 4 + 8 + 4 + 8 B per element (+ 4 / S for
             // the checkpoints each way) instead of 8 + 12 + 12 + 8; with 8 paths the second
             // pair adds into the running sum (12 B) and paths 4 .. 7 follow as sweeps
-            a.ck = B.ck;
+            a.ck = G.ck;
             const double ckb = 4.0 / sm::sgm_ck_seg(p.num_disparities);
-            const double nv = (double)n * c->nvol;
+            const double nv = (double)G.n * c->nvol;
             const bool four = p.sgm_paths == 4;
             struct Pass { int path, mode; const char* name; double per; };
             const Pass passes[4] = {
@@ -400,13 +388,13 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
                 a.ru = RU[ps.path];
                 a.dir = ps.path;
                 a.dir2 = ps.path + 1;
-                const double bytes = nv * ps.per + ((ps.mode & sm::SGM_LAST) ? (double)n * c->npix * 2 : 0);
-                const std::string name = std::string(ps.name) + sfx;
-                sm_status s = timed(c, name.c_str(), bytes, [&] { sm::launch_sgm_ck(a, ps.mode, n, c->st); });
+                const double bytes = nv * ps.per + ((ps.mode & sm::SGM_LAST) ? (double)G.n * c->npix * 2 : 0);
+                const std::string name = Group::name(ps.name, view);
+                sm_status s = timed(c, G.st, name.c_str(), bytes, [&] { sm::launch_sgm_ck(a, ps.mode, G.n, G.st); });
                 if (s) return s;
             }
             first = 4;
-            if (B.lx) {
+            if (G.lx) {
                 // 8 paths: the diagonal pair (4, 6) with L5 between them (sm_sgm.hip): pass A of
                 // path 4, path 5 as an SGM_FIRST sweep storing L5, pass B of path 6 reading acc and
                 // L5 (acc = ((acc + L4) + L5) + L6); path 7 follows as the last sweep
@@ -415,20 +403,20 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
                 a.ru = RU[4];
                 a.dir = 4;
                 a.dir2 = 6;
-                sm_status s = timed(c, (std::string("sgm_ck_a46") + sfx).c_str(), nv * (4.0 + ckd),
-                                    [&] { sm::launch_sgm_ck(a, sm::CK_A, n, c->st); });
+                sm_status s = timed(c, G.st, Group::name("sgm_ck_a46", view), nv * (4.0 + ckd),
+                                    [&] { sm::launch_sgm_ck(a, sm::CK_A, G.n, G.st); });
                 if (s) return s;
                 sm::SgmArgs a5 = a;
                 a5.rv = RV[5];
                 a5.ru = RU[5];
                 a5.dir = 5;
-                a5.acc = B.lx;   // SGM_FIRST stores 0 + L5 == L5 (path costs are never -0)
-                s = timed(c, (std::string("sgm_l5") + sfx).c_str(), nv * 8.0,
-                          [&] { sm::launch_sgm_path(a5, sm::SGM_FIRST, n, c->st); });
+                a5.acc = G.lx;   // SGM_FIRST stores 0 + L5 == L5 (path costs are never -0)
+                s = timed(c, G.st, Group::name("sgm_l5", view), nv * 8.0,
+                          [&] { sm::launch_sgm_path(a5, sm::SGM_FIRST, G.n, G.st); });
                 if (s) return s;
-                a.lx = B.lx;
-                s = timed(c, (std::string("sgm_ck_b46") + sfx).c_str(), nv * (16.0 + ckd),
-                          [&] { sm::launch_sgm_ck(a, sm::CK_B | sm::CK_MID | sm::CK_X, n, c->st); });
+                a.lx = G.lx;
+                s = timed(c, G.st, Group::name("sgm_ck_b46", view), nv * (16.0 + ckd),
+                          [&] { sm::launch_sgm_ck(a, sm::CK_B | sm::CK_MID | sm::CK_X, G.n, G.st); });
                 if (s) return s;
                 first = 7;
             }
@@ -440,77 +428,76 @@ sm_status run_optimize(sm_ctx* c, int n, int view, const Bufs& B) {
             int mode = (i == 0 ? sm::SGM_FIRST : 0) | (i == p.sgm_paths - 1 ? sm::SGM_LAST : 0);
             // algorithmic bytes per element: read C (+ read acc) (+ write acc | write final)
             double per = 4.0 + ((mode & sm::SGM_FIRST) ? 0 : 4.0) + ((mode & sm::SGM_LAST) ? (keep_final ? 4.0 : 0) : 4.0);
-            double bytes = (double)n * c->nvol * per + ((mode & sm::SGM_LAST) ? (double)n * c->npix * 2 : 0);
-            const std::string name = std::string((mode & sm::SGM_LAST) ? "sgm_last_wta" : NAMES[i]) + sfx;
-            sm_status s = timed(c, name.c_str(), bytes, [&] { sm::launch_sgm_path(a, mode, n, c->st); });
+            double bytes = (double)G.n * c->nvol * per + ((mode & sm::SGM_LAST) ? (double)G.n * c->npix * 2 : 0);
+            const std::string name = Group::name((mode & sm::SGM_LAST) ? "sgm_last_wta" : NAMES[i], view);
+            sm_status s = timed(c, G.st, name.c_str(), bytes, [&] { sm::launch_sgm_path(a, mode, G.n, G.st); });
             if (s) return s;
         }
     } else if (p.optimization == SM_OPT_SO) {
         // so(vm[i], DP[i], I_c) reads I[0] — the left colours — for both views (cpp:1098, 6284)
         sm::SoArgs a{};
         a.vm = vm;
-        a.trace = c->so_trace + (size_t)(B.disp - c->disp) * p.num_disparities;
-        a.cidx = c->so_cidx + (B.disp - c->disp);
-        a.px = B.px;
+        a.trace = G.slice(c->so_trace, c->nvol);
+        a.cidx = G.slice(c->so_cidx, c->npix);
+        a.px = G.px;
         a.disp = disp;
         a.H = p.rows;
         a.W = p.cols;
         a.D = p.num_disparities;
-        a.n = n;
+        a.n = G.n;
         a.keep_final = p.keep_final_volume;
-        const std::string name = std::string("so") + sfx;
-        sm_status s = timed(c, name.c_str(), (double)n * c->nvol * (4.0 + 1.0 + (p.keep_final_volume ? 4.0 : 0)),
-                            [&] { sm::launch_so(a, c->st); });
+        const std::string name = Group::name("so", view);
+        sm_status s = timed(c, G.st, name.c_str(), (double)G.n * c->nvol * (4.0 + 1.0 + (p.keep_final_volume ? 4.0 : 0)),
+                            [&] { sm::launch_so(a, G.st); });
         if (s) return s;
     } else if (!vmtop) {
-        const std::string name = std::string("wta") + sfx;
-        sm_status s = timed(c, name.c_str(), (double)n * c->nvol * 4.0 + (double)n * c->npix * 2,
-                            [&] { sm::launch_wta(vm, disp, n, p.rows, p.cols, p.num_disparities, c->st); });
+        const std::string name = Group::name("wta", view);
+        sm_status s = timed(c, G.st, name.c_str(), (double)G.n * c->nvol * 4.0 + (double)G.n * c->npix * 2,
+                            [&] { sm::launch_wta(vm, disp, G.n, p.rows, p.cols, p.num_disparities, G.st); });
         if (s) return s;
     }
-    if (vmtop) return run_vmtop(c, n, view, B, vm, disp);
+    if (vmtop) return run_vmtop(c, view, G, vm, disp);
     return SM_OK;
 }
 
 // refine(), non-USE_RECONCV branch (cpp:1347-1510), on DP[0] of n pairs: LR check (in place),
 // region votes and proper interpolations (Jacobi, ping-pong with disp_tmp), 3x3 median.
-sm_status run_refine(sm_ctx* c, int n, const Bufs& B) {
+sm_status run_refine(sm_ctx* c, const Group& G) {
     const sm_params& p = c->p;
     const int H = p.rows, W = p.cols;
-    const double map = (double)n * c->npix * 2;
-    sm_status s = timed(c, "refine_lr_check", 3 * map,
-                        [&] { sm::launch_lr_check(B.disp, B.disp1, n, H, W, p.lr_max_diff, c->st); });
+    const double map = (double)G.n * c->npix * 2;
+    sm_status s = timed(c, G.st, "refine_lr_check", 3 * map,
+                        [&] { sm::launch_lr_check(G.disp, G.disp1, G.n, H, W, p.lr_max_diff, G.st); });
     if (s) return s;
-    const size_t off = (size_t)(B.disp - c->disp);   // the group's first pixel
-    const double np = (double)n * c->npix;
+    const double np = (double)G.n * c->npix;
     if (c->rx_pkr) {   // calPKR + signDp_UsingPKR (cpp:1378-1383) on vm[0] as dispOptimize left it
         sm::PkrArgs a{};
-        a.vm = B.vm0;
-        a.mask = c->pkr_mask + off;
-        a.disp = B.disp;
+        a.vm = G.vm0;
+        a.mask = G.slice(c->pkr_mask, c->npix);
+        a.disp = G.disp;
         a.H = H;
         a.W = W;
         a.D = p.num_disparities;
-        a.n = n;
+        a.n = G.n;
         a.ratio = c->rx_ratio;
         a.disp_pkr = c->rx_disp_pkr;
-        if ((s = timed(c, "refine_pkr", (double)n * c->nvol * 4.0 + np * 5, [&] { sm::launch_pkr(a, c->st); }))) return s;
+        if ((s = timed(c, G.st, "refine_pkr", (double)G.n * c->nvol * 4.0 + np * 5, [&] { sm::launch_pkr(a, G.st); }))) return s;
         c->rx_pkr_ran = true;
     }
-    int16_t* cur = B.disp;
-    int16_t* nxt = B.disp_tmp;
-    const uint32_t* arms = (const uint32_t*)B.arms;
+    int16_t* cur = G.disp;
+    int16_t* nxt = G.disp_tmp;
+    const uint32_t* arms = (const uint32_t*)G.arms;
     if (p.do_region_vote)
         for (int i = 0; i < p.region_vote_nums; i++) {
-            if ((s = timed(c, "refine_region_vote", 2 * map,
-                           [&] { sm::launch_region_vote(cur, nxt, arms, n, H, W, p.rv_s, p.rv_ratio, c->st); })))
+            if ((s = timed(c, G.st, "refine_region_vote", 2 * map,
+                           [&] { sm::launch_region_vote(cur, nxt, arms, G.n, H, W, p.rv_s, p.rv_ratio, G.st); })))
                 return s;
             std::swap(cur, nxt);
         }
     if (p.do_proper_ipol)
         for (int i = 0; i < p.region_vote_nums; i++) {
-            if ((s = timed(c, "refine_proper_ipol", 2 * map,
-                           [&] { sm::launch_proper_ipol(cur, nxt, B.px, n, H, W, p.disp_occ, c->st); })))
+            if ((s = timed(c, G.st, "refine_proper_ipol", 2 * map,
+                           [&] { sm::launch_proper_ipol(cur, nxt, G.px, G.n, H, W, p.disp_occ, G.st); })))
                 return s;
             std::swap(cur, nxt);
         }
@@ -520,27 +507,27 @@ sm_status run_refine(sm_ctx* c, int n, const Bufs& B) {
         a.r = nxt;
         a.H = H;
         a.W = W;
-        a.n = n;
+        a.n = G.n;
         a.depth = c->rx_depth;
         // k_bg_r reads the map and writes r; k_bg_scan reads both and writes the map
-        if ((s = timed(c, "refine_bg_ipol", 4 * map, [&] { sm::launch_bg_ipol(a, c->st); }))) return s;
+        if ((s = timed(c, G.st, "refine_bg_ipol", 4 * map, [&] { sm::launch_bg_ipol(a, G.st); }))) return s;
         std::swap(cur, nxt);
     }
     if (c->rx_se) {   // subpixelEnhancement + medianBlur(SE, SE, 3) (cpp:1482-1495); DP[0] stays
-        float* raw = c->se_tmp + off;
-        float* out = c->se + off;
+        float* raw = G.slice(c->se_tmp, c->npix);
+        float* out = G.slice(c->se, c->npix);
         const int keep = c->rx_mode == SM_SE_FLOAT;
-        if ((s = timed(c, "refine_subpixel", np * (2 + 12 + 4), [&] {
-                 sm::launch_subpixel(cur, B.vm0, raw, n, H, W, p.num_disparities, keep, c->st);
+        if ((s = timed(c, G.st, "refine_subpixel", np * (2 + 12 + 4), [&] {
+                 sm::launch_subpixel(cur, G.vm0, raw, G.n, H, W, p.num_disparities, keep, G.st);
              })))
             return s;
-        if ((s = timed(c, "refine_median3_f32", np * 8, [&] { sm::launch_median3_f32(raw, out, n, H, W, c->st); }))) return s;
+        if ((s = timed(c, G.st, "refine_median3_f32", np * 8, [&] { sm::launch_median3_f32(raw, out, G.n, H, W, G.st); }))) return s;
         c->rx_se_ran = true;
     }
     if (p.do_last_median_blur) {
-        if ((s = timed(c, "refine_median3", 2 * map, [&] { sm::launch_median3(cur, nxt, n, H, W, c->st); }))) return s;
+        if ((s = timed(c, G.st, "refine_median3", 2 * map, [&] { sm::launch_median3(cur, nxt, G.n, H, W, G.st); }))) return s;
         std::swap(cur, nxt);
     }
-    if (cur != B.disp) HIP_TRY(c, hipMemcpyAsync(B.disp, cur, (size_t)map, hipMemcpyDeviceToDevice, c->st));
+    if (cur != G.disp) HIP_TRY(c, hipMemcpyAsync(G.disp, cur, (size_t)map, hipMemcpyDeviceToDevice, G.st));
     return SM_OK;
 }

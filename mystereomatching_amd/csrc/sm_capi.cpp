@@ -3,7 +3,7 @@
 // each reference interface), the pyramid weights, getters and setters (sm_download_subpixel among them, beside
 // the stage it reads), the features' *_config calls, profiling, sm_cal_err and the diagnostics.  The batch
 // path is sm_run.cpp, the stage drivers sm_stages.cpp and sm_stages_agg.cpp, parameter checks sm_validate.cpp.
-// No exceptions cross the ABI.  Compile-time A/B switch of this file: SM_NL_PIPE.
+// No exceptions cross the ABI.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,10 +14,6 @@
 #include <new>
 
 #include "sm_ctx.h"
-
-#ifndef SM_NL_PIPE
-#define SM_NL_PIPE 1   // sm_run: NL's prep and cost volume on the front stream (A/B switch)
-#endif
 
 // The weight band of one stream: at most this many bytes, whatever the image height or the batch
 // (both images' weights of as many image rows as fit; at least one row).
@@ -224,7 +220,7 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         if ((s = dalloc(c, &c->nl_mst, sm::nl_mst_scratch_bytes(p->rows, p->cols, cap)))) return s;
         if ((s = dalloc(c, &c->nl_adj, cap * c->npix))) return s;
         // sm_run's pipelined front (one view, SGM): two sets of cost volume and penalty flags
-        c->nl_pipe = SM_NL_PIPE && p->aggregation == SM_AGG_NL && p->optimization == SM_OPT_SGM && !right_view(*p);
+        c->nl_pipe = p->aggregation == SM_AGG_NL && p->optimization == SM_OPT_SGM && !right_view(*p);
         if (c->nl_pipe) {
             if ((s = dalloc(c, &c->nl_vc, 2 * cap * c->nvol + vpad))) return s;
             if ((s = dalloc(c, &c->nl_fl, 2 * cap * c->npix))) return s;

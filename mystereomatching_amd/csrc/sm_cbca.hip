@@ -37,6 +37,9 @@
 // Rejected designs (same-process A/B) live as patches in tools/experiments/:
 // workgroup-staged V arm words, several waves / columns per block, persistent V sweeps, a per-tile
 // safe-dividend test, and the timing probes that located the V gathers' cost.
+// Superseded and kept the same way: cbca_nsv2_unpipelined.patch (NsV2's second wave before it was
+// software-pipelined over tiles) and cbca_ring8_one_wave.patch (H NORM at lag 34 as one wave per
+// line on the 8-tile ring cycle, before HN2).
 // Superseded: cbca_h_scan_fused_cost.patch (the one-wave fusion of the censusGrad cost into the
 // first H scan, slower than the two kernels) by the multi-wave sweep k_cbca_hsc below.
 #include <float.h>
@@ -173,10 +176,10 @@ struct CbLine {
     // drops the third set's own-arm load, readlane, pkmin and 64-word gather per position
     // (full resolution 11.15 -> 9.91 ms, profiles/r3l, r3m).
     static constexpr bool REUSE2 = LAGC > 0 && !HORIZ && MODE == CB_NORM_SCAN;
-    // RING8 (H NORM at the reference's lag, a compile-time LAGC): the ring holds 8 tiles
-    // (2 lag + T + 1 = 79 -> 80 slots at T = 10), so an 8-tile loop knows every tile's ring slots at
-    // compile time: the window slots of position k are (constant - tail - 1, constant + head),
-    // with no per-position scalar wrap (4 SALU per position) and no ws bookkeeping
+    // RING8 (H NORM at the reference's lag, a compile-time LAGC; HN2's sweep, cbca_run_hn2): the
+    // ring holds 8 tiles (2 lag + T + 1 = 79 -> 80 slots at T = 10), so an 8-tile loop knows every
+    // tile's ring slots at compile time: the window slots of position k are (constant - tail - 1,
+    // constant + head), with no per-position scalar wrap (4 SALU per position) and no ws bookkeeping
     static constexpr bool RING8 = LAGC > 0 && HORIZ && MODE == CB_NORM &&
                                   (2 * LAGC + T + 1 + T - 1) / T * T == 8 * T;
     static_assert(!REUSE2 || (CbCfg<HORIZ, MODE>::PF == 3 && LAGC + T - 1 <= 4 * T),
@@ -352,16 +355,13 @@ struct CbLine {
     // start read the zeroed ring, which is exactly the reference's border case
     // out = S[i + head] (cal1DCost, h:1643-1715).  Only the two ends of a line (GUARD) test
     // whether an output position exists before storing it.
-    template <bool GUARD, int R, int RC = -1>
+    template <bool GUARD, int R>
     __device__ __forceinline__ void tile(const Tile& t, int j0) {
         uint32_t pi[T], pi2[T];
         // ring % T == 0 and ws % T == 0, so the tile's write slots ws .. ws+T-1 never wrap
-        // (RC >= 0: the tile's slot in the 8-tile ring cycle, all slots compile-time constants)
-        constexpr int RINGC = 8 * T;
-        const int wsv = RC >= 0 ? RC * T : ws;
-        float* w1 = r1 + wsv * 64 + lane;
-        uint16_t* wa = ra + wsv * 64 + lane;
-        const int si0 = RC >= 0 ? (RC * T - LAGC + 2 * RINGC) % RINGC : uwrap(ws - lag);   // slot of i = j0 - lag
+        float* w1 = r1 + ws * 64 + lane;
+        uint16_t* wa = ra + ws * 64 + lane;
+        const int si0 = uwrap(ws - lag);   // slot of i = j0 - lag
         // (NORM_SCAN: r2 holds position p's S2 at slot (p + lag) mod ring, so the tile's S2 writes
         // are slots ws .. ws + T - 1 and the slot of i2 = j0 - 2 lag in r2 is si0)
         const int i0 = j0 - lag;
@@ -398,8 +398,7 @@ struct CbLine {
         uint32_t ahv[T], atv[T];
 #pragma unroll
         for (int k = 0; k < T; k++) {
-            const uint32_t sp = RC >= 0 ? slot_pair_c(pi[k], (si0 + k) % RINGC)
-                                        : slot_pair(pi[k], si0 + k);   // slots of i - tail - 1, i + head
+            const uint32_t sp = slot_pair(pi[k], si0 + k);   // slots of i - tail - 1, i + head
             shv[k] = ring_at<1, 0>(sp);
             stv[k] = ring_at<0, 0>(sp);
             if (MODE != CB_SCAN) {
@@ -459,7 +458,7 @@ struct CbLine {
             for (int k = 0; k < T; k++)
                 store_tile(ob2, k, s2h[k] - s2t[k], !GUARD || (unsigned)(i20 + k) < (unsigned)len);
         }
-        if (RC < 0) ws = (ws + T == ring) ? 0 : ws + T;
+        ws = (ws + T == ring) ? 0 : ws + T;
         wrs = (wrs + T >= cbca_win_ring(T)) ? wrs + T - cbca_win_ring(T) : wrs + T;
     }
 
@@ -546,14 +545,14 @@ struct CbLine {
         for (int k = 0; k < T; k++) store_tile(ob, k, finish_norm(qv[k]), !GUARD || (unsigned)(i0 + k) < (unsigned)len);
     }
 
-    template <int R = 0, int RC = -1>   // R: the tile's slot in the four-tile loop (REUSE2 history)
+    template <int R = 0>   // R: the tile's slot in the four-tile loop (REUSE2 history)
     __device__ __forceinline__ void process(const Tile& t, int j0) {
         constexpr int stages = MODE == CB_NORM_SCAN ? 2 : 1;
         const int last_out = j0 + T - 1 - lag * stages;        // last output position of the tile
         if (j0 - lag >= 0 && last_out < len && (MODE != CB_NORM_SCAN || j0 - 2 * lag >= 0))
-            tile<false, R, RC>(t, j0);
+            tile<false, R>(t, j0);
         else
-            tile<true, R, RC>(t, j0);
+            tile<true, R>(t, j0);
     }
 };
 
@@ -593,9 +592,6 @@ struct CbLine {
 #ifndef SM_CB_T_NSV
 #define SM_CB_T_NSV 7
 #endif
-#ifndef SM_CB_NSV_VMWAIT
-#define SM_CB_NSV_VMWAIT 1   // one explicit vmcnt wait per tile for the stage-A inputs
-#endif
 // s_waitcnt immediate (gfx9 encoding) waiting for vmcnt <= n only
 __host__ __device__ constexpr int nsv_vmcnt(int n) { return ((n >> 4) << 14) | (0xf << 8) | (0x7 << 4) | (n & 0xf); }
 static_assert(nsv_vmcnt(60) == 0xCF7C, "s_waitcnt encoding");
@@ -603,21 +599,11 @@ constexpr int NSV_LAG = 34;
 #ifndef SM_CB_NSV2_PRIO
 #define SM_CB_NSV2_PRIO 2   // NsV2: s_setprio of the second wave (full res 7.12-7.46 -> 7.05-7.17 ms, Teddy 0.543 -> 0.540, profiles/r5pr)
 #endif
-#ifndef SM_CB_NSV2_PIPE
-#define SM_CB_NSV2_PIPE 1   // NsV2's second wave software-pipelined over tiles (cbca_run_nsv2; same-process A/B
-                            // with placement trials, profiles/r6i: 7.10-7.19 -> 6.87-7.09 ms at like placements)
-#endif
 #ifndef SM_CB_NSV2_SPLIT
-#define SM_CB_NSV2_SPLIT 2   // (pipelined) B1 positions read before C(n-1)'s stores: 4 reads each, <= 15 in flight
+#define SM_CB_NSV2_SPLIT 2   // B1 positions read before C(n-1)'s stores: 4 reads each, <= 15 in flight
 #endif
 #ifndef SM_CB_NSV_LA
 #define SM_CB_NSV_LA 3   // NsV tiles in flight (same-process A/B of the two-wave sweep, profiles/r5la: 2 7.09-7.14, 3 7.03-7.04, 4 9.79-9.81 ms)
-#endif
-#ifndef SM_CB_RING8_LA
-#define SM_CB_RING8_LA 6   // RING8 tiles in flight (same-process A/B, profiles/r5q: LA 3 5.11-5.18, 4 5.10, 5 5.10, 6 5.02-5.10, 7 5.13 ms)
-#endif
-#ifndef SM_CB_RING8
-#define SM_CB_RING8 1   // H NORM at lag 34 through CbLine::RING8 (0: the runtime-ring sweep, A/B builds)
 #endif
 constexpr int cbca_nsv_ring() { return (2 * NSV_LAG + SM_CB_T_NSV + 1 + SM_CB_T_NSV - 1) / SM_CB_T_NSV * SM_CB_T_NSV; }
 constexpr int cbca_nsv_phys() { return cbca_nsv_ring() + SM_CB_T_NSV - 1; }
@@ -715,33 +701,6 @@ struct NsV {
     // ring slot of output row i0 = j0 - LAG of the tile whose first input row sits at slot ws
     __device__ __forceinline__ static int out_slot(int ws) { return ws - LAG < 0 ? ws - LAG + R : ws - LAG; }
 
-    // stage B1: window slots of the normalised outputs at i = j - LAG (C: their first slot) and
-    // their S1 / area reads; the S1 addresses are kept for the scan stage LAG positions later
-    template <int RT>
-    __device__ __forceinline__ void stage_b1(const uint32_t (&pi)[T], int C, Norm& nm) {
-        typedef __attribute__((address_space(3))) const float lds_f;
-        typedef __attribute__((address_space(3))) const uint16_t lds_h;
-        const uint32_t cc = ((uint32_t)(C - 1) & 0xffffu) | ((uint32_t)C << 16);
-        const uint32_t ccr = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, cc) + __builtin_bit_cast(us2, RR));
-        // (all slot pairs first: the dependent packed ops of one position are not adjacent,
-        // which would cost s_nop wait states)
-        uint32_t spv[T];
-#pragma unroll
-        for (int k = 0; k < T; k++) spv[k] = slots(pi[k], cc, ccr);
-#pragma unroll
-        for (int k = 0; k < T; k++) {
-            const uint32_t sp = spv[k];
-            const uint32_t a1h = mad_u32_u16<1>(sp, 256u, o1), a1t = mad_u32_u16<0>(sp, 256u, o1);
-            hh[RT][k] = a1h;
-            ht[RT][k] = a1t;
-            nm.sh[k] = ((lds_f*)(size_t)a1h)[k * 64];
-            nm.st[k] = ((lds_f*)(size_t)a1t)[k * 64];
-            // (two positions' u16 ends share a register: the second a d16-hi read)
-            nm.ah[k / 2][k % 2] = ((lds_h*)(size_t)mad_u32_u16<1>(sp, 128u, oa))[k * 64];
-            nm.at[k / 2][k % 2] = ((lds_h*)(size_t)mad_u32_u16<0>(sp, 128u, oa))[k * 64];
-        }
-    }
-
     // stage B2: genfinalVm_cbca's division (cpp:3969-3992) of the outputs of tile j0, their
     // prefix S2 (iteration k+1's scan input) into the S2 ring at slots C .. C+T-1
     __device__ __forceinline__ void stage_b2(const Norm& nm, int C) {
@@ -808,9 +767,10 @@ struct NsV {
         }
     }
 
-    // NsV2 pipelined (SM_CB_NSV2_PIPE): B1's window addresses are formed a tile ahead (they need
-    // only the pass arms and the slot base), so that after the barrier "A(n) written" the reads
-    // issue back to back; the S1 ends go to the saved-address history hh / ht[RT] as in stage_b1
+    // stage B1: the window slots of the normalised outputs at i = j - LAG (C: their first slot) and
+    // their S1 / area reads.  The window addresses are formed a tile ahead (they need only the pass
+    // arms and the slot base), so that after the barrier "A(n) written" the reads issue back to
+    // back; the S1 addresses are kept in hh / ht[RT] for the scan stage LAG positions later
     struct B1Addr {
         uint32_t ah[T], at[T];   // the area ring's head / tail addresses
     };
@@ -873,15 +833,8 @@ struct NsV {
         for (int k = 0; k < T; k++) buf_st(ob2, xo[k], 0, s2h[k] - s2t[k]);
     }
 
-    __device__ __forceinline__ static void launder(Tile& t) {
-        static_assert(T == 7, "launder lists the 23 registers of a T = 7 tile");
-        asm volatile("" : "+v"(t.x[0]), "+v"(t.x[1]), "+v"(t.x[2]), "+v"(t.x[3]), "+v"(t.x[4]), "+v"(t.x[5]),
-                          "+v"(t.x[6]), "+v"(t.a0[0]), "+v"(t.a0[1]), "+v"(t.a1[0][0]), "+v"(t.a1[0][1]),
-                          "+v"(t.a1[0][2]), "+v"(t.a1[0][3]), "+v"(t.a1[0][4]), "+v"(t.a1[0][5]), "+v"(t.a1[0][6]),
-                          "+v"(t.a1[1][0]), "+v"(t.a1[1][1]), "+v"(t.a1[1][2]), "+v"(t.a1[1][3]), "+v"(t.a1[1][4]),
-                          "+v"(t.a1[1][5]), "+v"(t.a1[1][6]));
-    }
-    // (NsV2 pipelined: each wave waits for its own part of a tile only)
+    // one explicit vmcnt wait per tile for a wave's own part of it: the registers pass through an
+    // empty asm, so the wait sits here and not at each first use
     __device__ __forceinline__ static void launder_set1(Tile& t) {   // volume rows + set 1 (stage A)
         static_assert(T == 7, "launder lists a T = 7 tile");
         asm volatile("" : "+v"(t.x[0]), "+v"(t.x[1]), "+v"(t.x[2]), "+v"(t.x[3]), "+v"(t.x[4]), "+v"(t.x[5]),
@@ -940,7 +893,7 @@ struct NsV {
     }
 };
 
-// the line's state (both NsV forms); the caller zeroes the rings
+// the line's state; the caller zeroes the rings
 template <bool RV, bool CHECK>
 __device__ __forceinline__ void nsv_setup(NsV<RV, CHECK>& L, const CbcaArgs& a, const int blk, float* smem) {
     using L_t = NsV<RV, CHECK>;
@@ -1080,16 +1033,12 @@ __device__ __forceinline__ void cbca_run_nsv2(const CbcaArgs& a, const int blk, 
             __builtin_amdgcn_sched_barrier(0);
         }
         NSV_TR(NsvTrace tr; tr.start(); int tiles = 0;)
-        const int nst0 = SM_CB_NSV2_PIPE ? nst + T : nst;   // (the pipelined second wave's extra step)
+        const int nst0 = nst + T;   // (the second wave's extra step)
         for (int j0 = J0; j0 < nst0; j0 += 6 * T) {
             auto step = [&](auto rc) {
                 constexpr int n = decltype(rc)::value;
                 L.template load<false, 5>(tq[(n + LA) % 6]);
-#if SM_CB_NSV_VMWAIT && SM_CB_NSV2_PIPE
                 L_t::launder_set1(tq[n]);
-#elif SM_CB_NSV_VMWAIT
-                L_t::launder(tq[n]);
-#endif
                 typename L_t::AVals v;
                 L.stage_a_values(tq[n], v);
                 NSV_TR(tr.mark(0);)   // loads issued, tile n waited for, A(n) values
@@ -1112,108 +1061,57 @@ __device__ __forceinline__ void cbca_run_nsv2(const CbcaArgs& a, const int blk, 
 #if SM_CB_NSV2_PRIO
         __builtin_amdgcn_s_setprio(SM_CB_NSV2_PRIO);   // the second wave carries the critical chain
 #endif
-#if SM_CB_NSV2_PIPE
         // Software-pipelined over tiles: step n = X1(n) | B1(n) reads, first positions | C(n-1)'s
         // differences and stores (its reads, issued in step n-1, long returned) | B1(n) reads, the
         // rest | tile n+1's loads and pass intersections | X2(n) | B2(n) | C(n) reads (not waited
         // for) | B1(n+1)'s addresses.  So B1's LDS latency hides C(n-1)'s stores, C's LDS latency
         // hides the barrier and B1(n+1)'s issue, and the window X1(n) -> X2(n), in which the first
         // wave waits, holds only B1's reads.  C(n) of the last tile needs one more step.
-        {
-            typename L_t::Norm nm;
-            typename L_t::B1Addr ad;
-            int C = L_t::out_slot(0);
-            L.jst -= T;   // step 0 stores "C(-1)": rows before the line, out of range
-            L.xst -= (long)T * (long)L.vsb;
-            float s2h[T], s2t[T];
-            uint32_t pi[T];
-#pragma unroll
-            for (int k = 0; k < T; k++) s2h[k] = s2t[k] = 0.f;
-            // (the steady state's vmcnt sequence: T stores, then a tile's loads)
-            L.template load<false, 2>(tq[0]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 1; k <= LA; k++) {
-                L.dummy_stores();
-                __builtin_amdgcn_sched_barrier(0);
-                L.template load<false, 2>(tq[k]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            L_t::launder_set0(tq[0]);
-            L.pass_isect(tq[0], pi);
-            L.template b1_addr<0>(pi, C, ad);
-            nsv2_bar();   // (pairs with the first wave's "B1(-1) read")
-            const int nst1 = nst + T;
-            NSV_TR(NsvTrace tr; tr.start(); int tiles = 0;)
-            for (int j0 = J0; j0 < nst1; j0 += 6 * T) {
-                auto step = [&](auto rc) {
-                    constexpr int n = decltype(rc)::value;
-                    nsv2_bar();                                       // X1(n): A(n) written
-                    NSV_TR(tr.mark(0);)   // X2(n-1) -> X1(n): B2, C issue, B1 addresses, X1 wait (+ C(n-1) read wait)
-                    L.template b1_read<n, 0, SM_CB_NSV2_SPLIT>(ad, nm);
-                    __builtin_amdgcn_sched_barrier(0);
-                    L.stage_c_store(s2h, s2t);                        // C(n-1)
-                    __builtin_amdgcn_sched_barrier(0);
-                    L.template b1_read<n, SM_CB_NSV2_SPLIT, T>(ad, nm);
-                    __builtin_amdgcn_sched_barrier(0);
-                    L.template load<false, 2>(tq[(n + LA + 1) % 6]);
-                    L_t::launder_set0(tq[(n + 1) % 6]);
-                    L.pass_isect(tq[(n + 1) % 6], pi);
-                    nsv2_bar_lgkm();                                  // X2(n): B1(n) read
-                    NSV_TR(tr.mark(1); tiles++;)   // X1(n) -> X2(n): B1 reads, C(n-1) stores, loads, isect, X2
-                    L.stage_b2(nm, C);                                // B2(n)
-                    L.template stage_c_read<n>(s2h, s2t);             // C(n)
-                    C = C + T >= L_t::R ? C + T - L_t::R : C + T;
-                    L.template b1_addr<(n + 1) % 6>(pi, C, ad);       // (tile n + 1)
-                };
-                step(std::integral_constant<int, 0>{});
-                step(std::integral_constant<int, 1>{});
-                step(std::integral_constant<int, 2>{});
-                step(std::integral_constant<int, 3>{});
-                step(std::integral_constant<int, 4>{});
-                step(std::integral_constant<int, 5>{});
-            }
-            NSV_TR(tr.flush(blk, 1, tiles);)
-            return;
-        }
-#endif
         typename L_t::Norm nm;
+        typename L_t::B1Addr ad;
         int C = L_t::out_slot(0);
+        L.jst -= T;   // step 0 stores "C(-1)": rows before the line, out of range
+        L.xst -= (long)T * (long)L.vsb;
+        float s2h[T], s2t[T];
+        uint32_t pi[T];
+#pragma unroll
+        for (int k = 0; k < T; k++) s2h[k] = s2t[k] = 0.f;
+        // (the steady state's vmcnt sequence: T stores, then a tile's loads)
         L.template load<false, 2>(tq[0]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int k = 1; k < LA; k++) {
+        for (int k = 1; k <= LA; k++) {
+            L.dummy_stores();
+            __builtin_amdgcn_sched_barrier(0);
             L.template load<false, 2>(tq[k]);
             __builtin_amdgcn_sched_barrier(0);
-#if SM_CB_NSV_VMWAIT
-            L.dummy_stores();   // the stores of "C(k - LA)": step 0 sees the steady-state sequence
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
+        L_t::launder_set0(tq[0]);
+        L.pass_isect(tq[0], pi);
+        L.template b1_addr<0>(pi, C, ad);
         nsv2_bar();   // (pairs with the first wave's "B1(-1) read")
+        const int nst1 = nst + T;
         NSV_TR(NsvTrace tr; tr.start(); int tiles = 0;)
-        for (int j0 = J0; j0 < nst; j0 += 6 * T) {
+        for (int j0 = J0; j0 < nst1; j0 += 6 * T) {
             auto step = [&](auto rc) {
                 constexpr int n = decltype(rc)::value;
-                L.template load<false, 2>(tq[(n + LA) % 6]);
-#if SM_CB_NSV_VMWAIT
-                L_t::launder(tq[n]);
-#endif
-                uint32_t pi[T];
-                L.pass_isect(tq[n], pi);
-                NSV_TR(tr.mark(0);)   // loads issued, tile n waited for, pass intersections
-                nsv2_bar();                                   // A(n) written
-                NSV_TR(tr.mark(1);)   // waiting for A(n)
-                L.template stage_b1<n>(pi, C, nm);            // B1(n)
-                nsv2_bar_lgkm();                              // B1(n) read
-                NSV_TR(tr.mark(2);)   // B1 issue + LDS latency + barrier
-                L.stage_b2(nm, C);                            // B2(n)
-                NSV_TR(tr.mark(3);)   // B2 (includes its ring writes' completion: the one perturbation)
-                float s2h[T], s2t[T];
-                L.template stage_c_read<n>(s2h, s2t);         // C(n)
+                nsv2_bar();                                       // X1(n): A(n) written
+                NSV_TR(tr.mark(0);)   // X2(n-1) -> X1(n): B2, C issue, B1 addresses, X1 wait (+ C(n-1) read wait)
+                L.template b1_read<n, 0, SM_CB_NSV2_SPLIT>(ad, nm);
+                __builtin_amdgcn_sched_barrier(0);
+                L.stage_c_store(s2h, s2t);                        // C(n-1)
+                __builtin_amdgcn_sched_barrier(0);
+                L.template b1_read<n, SM_CB_NSV2_SPLIT, T>(ad, nm);
+                __builtin_amdgcn_sched_barrier(0);
+                L.template load<false, 2>(tq[(n + LA + 1) % 6]);
+                L_t::launder_set0(tq[(n + 1) % 6]);
+                L.pass_isect(tq[(n + 1) % 6], pi);
+                nsv2_bar_lgkm();                                  // X2(n): B1(n) read
+                NSV_TR(tr.mark(1); tiles++;)   // X1(n) -> X2(n): B1 reads, C(n-1) stores, loads, isect, X2
+                L.stage_b2(nm, C);                                // B2(n)
+                L.template stage_c_read<n>(s2h, s2t);             // C(n)
                 C = C + T >= L_t::R ? C + T - L_t::R : C + T;
-                L.stage_c_store(s2h, s2t);
-                NSV_TR(tr.mark(4); tiles++;)   // C reads + their latency + stores issued
+                L.template b1_addr<(n + 1) % 6>(pi, C, ad);       // (tile n + 1)
             };
             step(std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 1>{});
@@ -1350,33 +1248,7 @@ __device__ __forceinline__ void cbca_run_line(const CbcaArgs& a, const int blk, 
     // otherwise the compiler's vmcnt waits at the loop head are conservative and the first tile
     // of every trip waits for later tiles' loads too.  Tiles past the line end run (up to PF of
     // them): their loads are bounded or read the next line, their stores are out of range.
-    if constexpr (decltype(L)::RING8) {
-        // H NORM at lag 34: eight tiles per trip (one ring cycle), tile k in buffer k, LA tiles in
-        // flight (the buffer a load fills was consumed LA - 8 tiles before, LA <= 7)
-        typename CbLine<HORIZ, MODE, FULL, SCALE, RV, LAGC>::Tile tq[8];
-        constexpr int LA = SM_CB_RING8_LA;
-        static_assert(LA >= 1 && LA <= 7, "RING8 look-ahead");
-#pragma unroll
-        for (int k = 0; k < LA; k++) {
-            L.load(tq[k], k * T);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        for (int j0 = 0; j0 < nst; j0 += 8 * T) {
-            auto step = [&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                L.load(tq[(k + LA) % 8], j0 + (k + LA) * T);
-                L.template process<0, k>(tq[k], j0 + k * T);
-            };
-            step(std::integral_constant<int, 0>{});
-            step(std::integral_constant<int, 1>{});
-            step(std::integral_constant<int, 2>{});
-            step(std::integral_constant<int, 3>{});
-            step(std::integral_constant<int, 4>{});
-            step(std::integral_constant<int, 5>{});
-            step(std::integral_constant<int, 6>{});
-            step(std::integral_constant<int, 7>{});
-        }
-    } else if constexpr (CbCfg<HORIZ, MODE>::PF == 3) {
+    if constexpr (CbCfg<HORIZ, MODE>::PF == 3) {
         L.load(ta, 0);
         __builtin_amdgcn_sched_barrier(0);
         L.load(tb, T);
@@ -1426,10 +1298,8 @@ __device__ __forceinline__ void cbca_run_line(const CbcaArgs& a, const int blk, 
 // ring reads (the only reads A(n + 1) can overwrite: 2 lag + T + 1 <= 8 T slots).  The second wave
 // issues tile n + 1's set-0 staging and pass intersections while B(n)'s reads are in flight, and
 // runs B(n)'s division and stores while the first wave writes A(n + 1).
-#ifndef SM_CB_HN2
-#define SM_CB_HN2 1   // H NORM at lag 34 as HN2 (two waves per line; same-process A/B with placement trials,
-                      // profiles/r6/ab_hn2_fullres.txt: 5.00-5.02 -> 4.53-4.55 ms; 0: the one-wave RING8 sweep)
-#endif
+// (same-process A/B against the one-wave RING8 sweep with placement trials,
+// profiles/r6/ab_hn2_fullres.txt: 5.00-5.02 -> 4.53-4.55 ms)
 #ifndef SM_CB_HN2_LA
 #define SM_CB_HN2_LA 4   // HN2 tiles in flight (8 buffers; LA 6: 4.54-4.55 ms, 4: 4.53-4.55)
 #endif
@@ -1790,24 +1660,27 @@ __global__ __launch_bounds__(64 * (1 + HSC_NCW)) void k_cbca_hsc(const CbcaArgs 
     }
 }
 
-template <bool FULL, bool RV>
-static void launch_hsc_cw(const CbcaArgs& a, dim3 grid, dim3 block, size_t shm, hipStream_t st) {
-    if (a.cwords == 3) hipLaunchKernelGGL((k_cbca_hsc<FULL, RV, 3>), grid, block, shm, st, a);
-    else hipLaunchKernelGGL((k_cbca_hsc<FULL, RV, 4>), grid, block, shm, st, a);
+// the two runtime booleans of a launch as template arguments: f(bool_constant<x>, bool_constant<y>)
+template <typename F>
+static void with_bools(bool x, bool y, F f) {
+    if (x) {
+        if (y) f(std::true_type{}, std::true_type{});
+        else f(std::true_type{}, std::false_type{});
+    } else {
+        if (y) f(std::false_type{}, std::true_type{});
+        else f(std::false_type{}, std::false_type{});
+    }
 }
 
 void launch_cbca_hsc(const CbcaArgs& a, int n, hipStream_t st) {
     const int nchunks = (a.D + 63) / 64;
     dim3 grid(a.H * nchunks * n), block(64 * (1 + HSC_NCW));
     const size_t shm = 4 * (size_t)hsc_smem_words(a.lag, a.cwords);
-    const bool full = a.D % 64 == 0;
-    if (a.view == 0) {
-        if (full) launch_hsc_cw<true, false>(a, grid, block, shm, st);
-        else launch_hsc_cw<false, false>(a, grid, block, shm, st);
-    } else {
-        if (full) launch_hsc_cw<true, true>(a, grid, block, shm, st);
-        else launch_hsc_cw<false, true>(a, grid, block, shm, st);
-    }
+    with_bools(a.D % 64 == 0, a.view != 0, [&](auto full, auto rv) {
+        constexpr bool FULL = decltype(full)::value, RV = decltype(rv)::value;
+        if (a.cwords == 3) hipLaunchKernelGGL((k_cbca_hsc<FULL, RV, 3>), grid, block, shm, st, a);
+        else hipLaunchKernelGGL((k_cbca_hsc<FULL, RV, 4>), grid, block, shm, st, a);
+    });
 }
 
 template <bool HORIZ, int MODE, bool FULL, bool SCALE, bool RV, int LAGC = 0>
@@ -1822,15 +1695,10 @@ static void launch_lag(const CbcaArgs& a, int n, hipStream_t st) {
     const int nchunks = (a.D + 63) / 64;
     const int nlines = (HORIZ ? a.H : a.W) * nchunks * n;
     const size_t shm = 4 * (size_t)cbca_smem_words(a.lag, HORIZ, MODE);
-    const bool full = a.D % 64 == 0;
     dim3 grid(nlines), block(64);
-    if (a.view == 0) {
-        if (full) hipLaunchKernelGGL((k_cbca<HORIZ, MODE, true, SCALE, false, LAGC>), grid, block, shm, st, a);
-        else hipLaunchKernelGGL((k_cbca<HORIZ, MODE, false, SCALE, false, LAGC>), grid, block, shm, st, a);
-    } else {
-        if (full) hipLaunchKernelGGL((k_cbca<HORIZ, MODE, true, SCALE, true, LAGC>), grid, block, shm, st, a);
-        else hipLaunchKernelGGL((k_cbca<HORIZ, MODE, false, SCALE, true, LAGC>), grid, block, shm, st, a);
-    }
+    with_bools(a.D % 64 == 0, a.view != 0, [&](auto full, auto rv) {
+        hipLaunchKernelGGL((k_cbca<HORIZ, MODE, decltype(full)::value, SCALE, decltype(rv)::value, LAGC>), grid, block, shm, st, a);
+    });
 }
 
 // NsV's prerequisites: the reference's lag, whole 64-disparity chunks, arm-plane offsets in 31 bits
@@ -1846,36 +1714,24 @@ static void launch_scaled(const CbcaArgs& a, int n, hipStream_t st) {
         if (nsv_ok(a)) {
             dim3 grid(a.W * (a.D / 64) * n), block(128);   // two waves per line
             const size_t shm = 4 * (size_t)cbca_nsv_smem_words();
-            if (a.view == 0) {
-                if (a.div_safe) hipLaunchKernelGGL((k_cbca_nsv2<false, false>), grid, block, shm, st, a);
-                else hipLaunchKernelGGL((k_cbca_nsv2<false, true>), grid, block, shm, st, a);
-            } else {
-                if (a.div_safe) hipLaunchKernelGGL((k_cbca_nsv2<true, false>), grid, block, shm, st, a);
-                else hipLaunchKernelGGL((k_cbca_nsv2<true, true>), grid, block, shm, st, a);
-            }
+            with_bools(a.view != 0, !a.div_safe, [&](auto rv, auto check) {
+                hipLaunchKernelGGL((k_cbca_nsv2<decltype(rv)::value, decltype(check)::value>), grid, block, shm, st, a);
+            });
             return;
         }
         if (a.lag == 34) return launch_lag<HORIZ, MODE, SCALE, 34>(a, n, st);
     }
-#if SM_CB_RING8
-    // H NORM at the reference's lag: the compile-time 8-tile ring cycle (CbLine::RING8)
+    // H NORM at the reference's lag: HN2, two waves per line on the compile-time 8-tile ring cycle
     if constexpr (HORIZ && MODE == CB_NORM) {
-        if (a.lag == 34 && SM_CB_HN2) {   // two waves per line (HN2)
+        if (a.lag == 34) {
             dim3 grid(a.H * ((a.D + 63) / 64) * n), block(128);
             const size_t shm = 4 * (size_t)cbca_smem_words(a.lag, true, CB_NORM);
-            const bool full = a.D % 64 == 0;
-            if (a.view == 0) {
-                if (full) hipLaunchKernelGGL((k_cbca_hn2<true, SCALE, false>), grid, block, shm, st, a);
-                else hipLaunchKernelGGL((k_cbca_hn2<false, SCALE, false>), grid, block, shm, st, a);
-            } else {
-                if (full) hipLaunchKernelGGL((k_cbca_hn2<true, SCALE, true>), grid, block, shm, st, a);
-                else hipLaunchKernelGGL((k_cbca_hn2<false, SCALE, true>), grid, block, shm, st, a);
-            }
+            with_bools(a.D % 64 == 0, a.view != 0, [&](auto full, auto rv) {
+                hipLaunchKernelGGL((k_cbca_hn2<decltype(full)::value, SCALE, decltype(rv)::value>), grid, block, shm, st, a);
+            });
             return;
         }
-        if (a.lag == 34) return launch_lag<HORIZ, MODE, SCALE, 34>(a, n, st);
     }
-#endif
     launch_lag<HORIZ, MODE, SCALE, 0>(a, n, st);
 }
 

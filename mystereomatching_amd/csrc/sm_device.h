@@ -24,13 +24,6 @@
      0x3feee89f995ad3adULL, 0x3feeff76f2fb5e47ULL, 0x3fef199bdd85529cULL, 0x3fef3720dcef9069ULL, \
      0x3fef5818dcfba487ULL, 0x3fef7c97337b9b5fULL, 0x3fefa4afa2a490daULL, 0x3fefd0765b6e4540ULL}
 
-#ifndef SM_EXPF_VEC
-#define SM_EXPF_VEC 1   // assemble 2^(k/32) from two 32-bit words (4 VALU fewer per call than 64-bit ops)
-#endif
-#ifndef SM_EXPF_FMA_SHIFT
-#define SM_EXPF_FMA_SHIFT 1
-#endif
-
 namespace sm {
 
 // entry ki % 32 of the 2^(i/32) table (overloaded for the cost kernel's LDS copy)
@@ -48,29 +41,20 @@ __host__ __device__ inline float expf_glibc_core(float x, const Tab& tab) {
     const double C1 = 0x1.ebfce50fac4f3p-3 / 32 / 32;
     const double C2 = 0x1.62e42ff0c52d6p-1 / 32;
     double xd = (double)x;
-#if SM_EXPF_FMA_SHIFT
     // kd = round(InvLn2N * xd) through one fma instead of a rounded product plus SHIFT: equal
     // to glibc's result on every float the device path sees (tests/test_gpu_parity.py,
     // test_device_expf_exhaustive: all of [-104, -0])
     double kd = __builtin_fma(InvLn2N, xd, SHIFT);
-#else
-    double z = InvLn2N * xd;
-    double kd = z + SHIFT;
-#endif
     uint64_t ki = __builtin_bit_cast(uint64_t, kd);
     kd -= SHIFT;
     double r = __builtin_fma(InvLn2N, xd, -kd);
     const uint64_t t = exp_tab_at(tab, ki);
     // t += ki << 47: the shifted term's low word is 0, so only the high word changes (one
     // 32-bit add instead of a 64-bit shift and add); the words are assembled as a 2-vector so
-    // that no 64-bit shift / or is emitted for the pair
-#if SM_EXPF_VEC
+    // that no 64-bit shift / or is emitted for the pair (4 VALU fewer per call)
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     const u32x2 tw = {(uint32_t)t, (uint32_t)(t >> 32) + ((uint32_t)ki << 15)};
     double s = __builtin_bit_cast(double, tw);
-#else
-    double s = __builtin_bit_cast(double, (t & 0xffffffffull) | ((uint64_t)((uint32_t)(t >> 32) + ((uint32_t)ki << 15)) << 32));
-#endif
     double zz = __builtin_fma(C0, r, C1);
     double r2 = r * r;
     double y = __builtin_fma(C2, r, 1.0);
@@ -123,7 +107,7 @@ __device__ __forceinline__ uint32_t buf_ld_u32(__amdgpu_buffer_rsrc_t r, uint32_
 }
 // Volume stores are streaming: every pass writes a W x H x D volume larger than the 256 MB
 // Infinity Cache, read back only by the next pass.  SM_ST_AUX = 2 (slc = "nt" on gfx950) sends
-// them with the non-temporal policy, as does SM_NT_STORES for the SGM path sums.  Measured (Teddy
+// them with the non-temporal policy, as does st_stream for the SGM path sums.  Measured (Teddy
 // x16, same box): the pass after a plain-store pass runs slower while the Infinity Cache writes
 // back the previous pass's dirty lines — cost volume nt: h_scan 0.314 -> 0.272 ms; CBCA nt:
 // -0.005 ms per sweep; SGM nt: path1 0.392 -> 0.370 ms; 3.53 -> ~3.43 ms per step together.
@@ -133,43 +117,18 @@ __device__ __forceinline__ uint32_t buf_ld_u32(__amdgpu_buffer_rsrc_t r, uint32_
 __device__ __forceinline__ void buf_st(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, (int)voff, (int)soff, SM_ST_AUX);
 }
-#ifndef SM_NT_STORES
-#define SM_NT_STORES 1
-#endif
-__device__ __forceinline__ void st_stream(float* p, float v) {
-#if SM_NT_STORES
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-#ifndef SM_NT_LOADS
-#define SM_NT_LOADS 1   // SGM C / path-sum loads non-temporal: last path 0.302 -> 0.249 ms (Teddy x16)
-#endif
-__device__ __forceinline__ float ld_stream(const float* p) {
-#if SM_NT_LOADS
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ void st_stream(float* p, float v) { __builtin_nontemporal_store(v, p); }
+// (SGM C / path-sum loads non-temporal: last path 0.302 -> 0.249 ms, Teddy x16)
+__device__ __forceinline__ float ld_stream(const float* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ float4 ld_stream4(const float* p) {
-#if SM_NT_LOADS
     return make_float4(__builtin_nontemporal_load(p), __builtin_nontemporal_load(p + 1), __builtin_nontemporal_load(p + 2),
                        __builtin_nontemporal_load(p + 3));
-#else
-    return *(const float4*)p;
-#endif
 }
 __device__ __forceinline__ void st_stream4(float* p, float4 v) {
-#if SM_NT_STORES
     __builtin_nontemporal_store(v.x, p);
     __builtin_nontemporal_store(v.y, p + 1);
     __builtin_nontemporal_store(v.z, p + 2);
     __builtin_nontemporal_store(v.w, p + 3);
-#else
-    *(float4*)p = v;
-#endif
 }
 
 // a / b for a float a >= 0 and an integer 1 <= b < 2^16 (CBCA support areas), correctly

@@ -106,37 +106,11 @@ __global__ __launch_bounds__(256) void k_gf_img_v(const uint32_t* __restrict__ p
 // sequential cumulative sum on the LDS copy (a lane per row reading global memory directly makes
 // every load instruction touch 64 rows).  Block j0 reads columns j0 .. j0 + 19 and writes the
 // outputs of columns j0 - 9 .. j0 + 10, all of which it has already read (in place is safe).
-#ifndef SM_GF_IMG_H_LDS
-#define SM_GF_IMG_H_LDS 1
-#endif
 constexpr int GF_HP = GF_RING + 1;   // LDS row pitch (odd: conflict-free column reads)
 __global__ __launch_bounds__(64) void k_gf_img_h(float* __restrict__ planes, int H, int W, int n) {
     const int rows = n * 10 * H;
     const int lane = threadIdx.x;
     const int r0 = blockIdx.x * 64;
-    if (!SM_GF_IMG_H_LDS) {
-        const int t = r0 + lane;
-        if (t >= rows) return;
-        float* row = planes + (size_t)t * W;   // planes are [b][k][H][W]: thread t owns row t
-        float ring[GF_RING];
-        float S = 0.f;
-        for (int j0 = 0; j0 < W + GF_R; j0 += GF_RING) {
-            float vin[GF_RING];
-#pragma unroll
-            for (int s = 0; s < GF_RING; s++) vin[s] = j0 + s < W ? row[j0 + s] : 0.f;
-#pragma unroll
-            for (int s = 0; s < GF_RING; s++) {
-                const int j = j0 + s;
-                if (j < W + GF_R) {
-                    if (j < W) S = (j == 0) ? vin[0] : S + vin[s];   // CumSum(., 2): x = 0 copies
-                    ring[s] = S;
-                    const int i = j - GF_R;
-                    if (i >= 0) row[i] = i >= GF_R + 1 ? S - ring[(s + 1) % GF_RING] : S;
-                }
-            }
-        }
-        return;
-    }
     __shared__ float tin[64 * GF_HP], tout[64 * GF_HP];
     // element m of a lane's share of a block: row (m * 64 + lane) / GF_RING, column % GF_RING
     auto fetch = [&](float (&v)[GF_RING], int j0) {

@@ -37,11 +37,8 @@ namespace {
 
 constexpr int GC_R = 9;              // gf_r[0] (h:297)
 constexpr int GC_K = 2 * GC_R + 1;   // box size
-#ifndef SM_GFCV_RING
-#define SM_GFCV_RING 1   // column sweeps keep the window's row sums in a register ring (k_gfcv_cols)
-#endif
 #ifndef SM_GFCV_PF
-#define SM_GFCV_PF 3     // rows of row sums prefetched ahead by the ring form (divides 18)
+#define SM_GFCV_PF 3     // rows of row sums prefetched ahead by the column sweeps (divides 18)
 #endif
 
 // OpenCV borderInterpolate(BORDER_REFLECT) for len >= GC_R (one reflection suffices)
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(256) void k_gfcv_pix(float* __restrict__ pix, int H
 }
 
 #ifndef SM_GFCV_T
-#define SM_GFCV_T 4   // positions per prefetched tile of the volume sweeps (two tiles in flight)
+#define SM_GFCV_T 4   // positions per prefetched tile of the row sweeps (two tiles in flight)
 #endif
 
 // ---------------------------------------------------------------------------------------------
@@ -262,7 +259,6 @@ __global__ __launch_bounds__(64) void k_gfcv_rows(const GfCvArgs a) {
 // ---------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(64) void k_gfcv_cols(const GfCvArgs a) {
-    constexpr int T = SM_GFCV_T;
     const int lane = threadIdx.x;
     const int nchunks = (a.D + 63) >> 6;
     const int blk = xcd_swizzle(blockIdx.x, gridDim.x);
@@ -343,10 +339,10 @@ __global__ __launch_bounds__(64) void k_gfcv_cols(const GfCvArgs a) {
         }
     };
     double SUM[4] = {0, 0, 0, 0};
-#if SM_GFCV_RING
     // The row sums leaving the window (row y - r) are the ones that entered it 2r = 18 rows
     // earlier: a register ring of 18 rows x 4 channels keeps them, so every RS element is read
-    // once (the tiled form below reads it twice, the second time 18 rows later, past L2).
+    // once (the tiled form, tools/experiments/gfcv_cols_tiled.patch, read it twice, the second
+    // time 18 rows later, past L2).
     // ring[i] starts as row refl(i - r), the rows the first 18 outputs drop; slot y mod 18.
     constexpr int RK = GC_K - 1, PF = SM_GFCV_PF;
     static_assert(RK % PF == 0, "prefetch slots repeat with the ring");
@@ -386,53 +382,6 @@ __global__ __launch_bounds__(64) void k_gfcv_cols(const GfCvArgs a) {
             emit(y, m);
         }
     }
-#else
-    for (int i = 0; i < GC_K - 1; i++) {
-        const size_t e = col0 + (size_t)refl(i - GC_R, H) * rstep;
-#pragma unroll
-        for (int c = 0; c < 4; c++) SUM[c] += rs[c * rs_plane + e];
-    }
-    struct Tile {
-        double sp[T][4];
-        double sm[T][4];
-    };
-    auto load = [&](Tile& t, int y0) {
-#pragma unroll
-        for (int s = 0; s < T; s++) {
-            const int y = min(y0 + s, H - 1);
-            const size_t ep = col0 + (size_t)refl(y + GC_R, H) * rstep, em = col0 + (size_t)refl(y - GC_R, H) * rstep;
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                t.sp[s][c] = rs[c * rs_plane + ep];
-                t.sm[s][c] = rs[c * rs_plane + em];
-            }
-        }
-    };
-    auto process = [&](const Tile& t, int y0) {
-#pragma unroll
-        for (int s = 0; s < T; s++) {
-            const int y = y0 + s;
-            if (y >= H) break;   // wave-uniform
-            float m[4];
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const double s0 = SUM[c] + t.sp[s][c];
-                m[c] = (float)(s0 * scale);
-                SUM[c] = s0 - t.sm[s][c];
-            }
-            emit(y, m);
-        }
-    };
-    Tile ta, tb;
-    load(ta, 0);
-    for (int y0 = 0; y0 < H; y0 += 2 * T) {
-        load(tb, y0 + T);
-        process(ta, y0);
-        if (y0 + T >= H) break;
-        load(ta, y0 + 2 * T);
-        process(tb, y0 + T);
-    }
-#endif
 }
 
 }  // namespace

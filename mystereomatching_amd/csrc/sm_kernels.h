@@ -12,7 +12,6 @@ enum { SM_M_SD = 4, SM_M_BT = 5, SM_M_GRAD = 6, SM_M_TRUNC_AD = 8, SM_M_AD_GRAD 
 enum { SGM_FIRST = 1, SGM_LAST = 2, SGM_KEEP = 4, SGM_SIGNED = 8 };  // KEEP: last path also writes the summed volume;
 // SIGNED: costs may be negative (the guided filter's output), minima compare as floats
 enum { CB_SCAN = 0, CB_NORM = 1, CB_NORM_SCAN = 2 };
-constexpr int CBCA_TILE = 16;  // steps of lookahead per wave in the CBCA line sweeps
 
 struct PrepArgs {
     const uint8_t* gray;        // [n][2][H][W]

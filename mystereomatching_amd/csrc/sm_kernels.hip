@@ -151,9 +151,6 @@ __device__ __forceinline__ bool ok10(uint32_t c, uint32_t p, uint32_t ka, uint32
 }
 constexpr uint32_t PREP_OUT = 0xffffffffu;   // packed-pixel strips: a pixel outside the image
 
-#ifndef SM_PREP_WALK
-#define SM_PREP_WALK 1    // arm-walk steps whose LDS reads are issued together (tuning)
-#endif
 // census code (genCensusCode_NC_Sur, h:867-934) and x/y gradients of one pixel; g = the pixel in
 // the block's gray tile (row stride gw, REFLECT_101 halo of max(rv, 1) rows / max(ru, 1) columns)
 template <int TRV, int TRU, int TRING>
@@ -243,30 +240,11 @@ __device__ __forceinline__ int strip_walk(const uint32_t* sp, int sst, uint32_t 
     const uint32_t want = ARM_B9 | fb;
     auto pass = [&](uint32_t p, uint32_t ca, uint32_t cb) { return ((((ca - p) & ~(cb - p)) & ARM_B9) | (p & fb)) == want; };
     int arm = 1;
-#if SM_PREP_WALK > 1
-    // chunks of SM_PREP_WALK steps: a chunk's LDS reads are issued together, then its first
-    // failing step (or Lo + 1) ends the walk
-    for (;;) {
-        uint32_t pw[SM_PREP_WALK];
-#pragma unroll
-        for (int j = 0; j < SM_PREP_WALK; j++) pw[j] = sp[min(arm + j, Lo) * sst];
-        int ff = SM_PREP_WALK;
-#pragma unroll
-        for (int j = SM_PREP_WALK - 1; j >= 0; j--) {
-            const int st = arm + j;
-            const bool in1 = st <= Lin;
-            if (st > Lo || !pass(pw[j], in1 ? ca1 : ca2, in1 ? cb1 : cb2)) ff = j;
-        }
-        arm += ff;
-        if (ff < SM_PREP_WALK) break;
-    }
-#else
     for (; arm <= Lin; arm++)
         if (!pass(sp[arm * sst], ca1, cb1)) break;
     if (arm > Lin)
         for (; arm <= Lo; arm++)
             if (!pass(sp[arm * sst], ca2, cb2)) break;
-#endif
     return arm;
 }
 // Two walks from one centre (the split prep's L / R and U / D pairs) advanced together in chunks
@@ -444,7 +422,7 @@ __global__ __launch_bounds__(256) void k_prep(const PrepArgs a) {
 
 
 // ---------------------------------------------------------------------------------------
-// Split prep (SM_PREP_SPLIT): two kernels that make the arm-walk words in LDS from the colour
+// Split prep: two kernels that make the arm-walk words in LDS from the colour
 // bytes, so no packed plane (px / pxh / pxv) goes through HBM, and whose tiles are long along
 // their walk axis, so the walk halo is re-read 1.3-2.1 times instead of the 16-row tile's 5.3:
 //   k_prep_h  tiles of 256 columns x 8 rows: census, the SGM penalty flags and the
@@ -454,9 +432,6 @@ __global__ __launch_bounds__(256) void k_prep(const PrepArgs a) {
 //             v0 - Lo - 1 .. v0 + 128 + Lo.
 // The packed-BGR plane is made (k_pack_bgr) only for the kernels that read it (GF, so, refine).
 // ---------------------------------------------------------------------------------------
-#ifndef SM_PREP_SPLIT
-#define SM_PREP_SPLIT 1
-#endif
 #ifndef SM_PREP_HTH
 #define SM_PREP_HTH 8    // k_prep_h tile rows (4 -> 8: gray / colour halo re-reads 2.5 / 1.5 -> 1.75 / 1.25)
 #endif
@@ -465,9 +440,6 @@ __global__ __launch_bounds__(256) void k_prep(const PrepArgs a) {
                          // 0.772 -> 0.736 ms at full resolution, profiles/r6/prep)
 #endif
 constexpr int PH_TW = 256, PH_TH = SM_PREP_HTH, PV_TW = 64, PV_TH = SM_PREP_VTH;
-#ifndef SM_PREP_QUAD
-#define SM_PREP_QUAD 1   // strips filled four pixels per load_quad_bgr (else three byte loads per pixel)
-#endif
 __host__ __device__ inline int preph_gray_bytes(int rv, int ru) {
     const int hv = rv > 1 ? rv : 1, hu = ru > 1 ? ru : 1;
     return ((PH_TW + 2 * hu) * (PH_TH + 2 * hv) + 15) / 16 * 16;
@@ -476,12 +448,6 @@ __host__ __device__ inline int preph_hc(int Lo) { return PH_TW + 2 * Lo + 2; }
 __host__ __device__ inline int preph_bytes(int rv, int ru, int Lo) { return preph_gray_bytes(rv, ru) + 4 * (PH_TH + 2) * preph_hc(Lo); }
 __host__ __device__ inline int prepv_bytes(int Lo) { return 4 * (PV_TH + 2 * Lo + 2) * PV_TW; }
 
-// packed pixel (pack10) of image pixel (vv, uu) from the colour bytes, PREP_OUT outside the image
-__device__ __forceinline__ uint32_t pack10_at(const uint8_t* bgr, int vv, int uu, int H, int W) {
-    if ((unsigned)vv >= (unsigned)H || (unsigned)uu >= (unsigned)W) return PREP_OUT;
-    const uint8_t* q = bgr + ((size_t)vv * W + uu) * 3;
-    return (uint32_t)q[0] | ((uint32_t)q[1] << 10) | ((uint32_t)q[2] << 20);
-}
 // Four consecutive pixels' colours (B | G << 8 | R << 16 each) from the 12 bytes at q, any
 // alignment: four dword loads from the dword below q and three byte-aligning funnel shifts (the
 // colour allocation carries a 16-byte tail pad for the fourth dword)
@@ -590,15 +556,7 @@ __global__ __launch_bounds__(256) void k_prep_h(const PrepArgs a) {
     uint32_t* PH = (uint32_t*)(prep_raw + preph_gray_bytes(rv, ru));   // [PH_TH + 2][hc]
     if (words || flags) {
         const uint8_t* C = a.bgr + img * npix * 3;
-        if (SM_PREP_QUAD) {
-            fill_strip_quads(PH, hc, C, v0 - 1, PH_TH + 2, u0 - Lo - 1, hc, H, W);
-        } else {
-            const float rinv = 1.0f / (float)hc;   // row by a float reciprocal (exact for i < 2^22)
-            prep_fill(PH, (PH_TH + 2) * hc, [&](int i) -> uint32_t {
-                const int r = (int)(((float)i + 0.5f) * rinv);
-                return pack10_at(C, v0 - 1 + r, u0 - Lo - 1 + (i - r * hc), H, W);
-            });
-        }
+        fill_strip_quads(PH, hc, C, v0 - 1, PH_TH + 2, u0 - Lo - 1, hc, H, W);
     }
     __syncthreads();
     if (flags) {   // SGM penalty flags (updateCost, h:2223-2229) from the packed pixels and their rim
@@ -690,12 +648,7 @@ __global__ __launch_bounds__(256) void k_prep_v(const PrepArgs a) {
     const int tid = threadIdx.x;
     uint32_t* PV = (uint32_t*)prep_raw;   // [PV_TH + 2 Lo + 2][PV_TW]: rows v0 - Lo - 1 ..
     const uint8_t* C = a.bgr + img * npix * 3;
-    if (SM_PREP_QUAD) {
-        fill_strip_quads(PV, PV_TW, C, v0 - Lo - 1, PV_TH + 2 * Lo + 2, u0, PV_TW, H, W);
-    } else {
-        prep_fill(PV, (PV_TH + 2 * Lo + 2) * PV_TW,
-                  [&](int i) -> uint32_t { return pack10_at(C, v0 - Lo - 1 + (i >> 6), u0 + (i & 63), H, W); });
-    }
+    fill_strip_quads(PV, PV_TW, C, v0 - Lo - 1, PV_TH + 2 * Lo + 2, u0, PV_TW, H, W);
     __syncthreads();
     {
         const int tc = min(max(a.C_D, -1), 255);
@@ -779,7 +732,7 @@ static void launch_prep_split(const PrepArgs& a, int n, hipStream_t st) {
 
 void launch_prep(const PrepArgs& a, int n, hipStream_t st) {
     const bool strips = a.do_arms && prep_strips(a.L_out);
-    const bool split = SM_PREP_SPLIT && (strips || !a.do_arms);
+    const bool split = strips || !a.do_arms;
     if (split && !a.pack_px) {
         launch_prep_split(a, n, st);
         return;
@@ -833,20 +786,8 @@ void launch_prep(const PrepArgs& a, int n, hipStream_t st) {
 #ifndef SM_COST_STORE_AUX
 #define SM_COST_STORE_AUX 2   // buffer store cache policy: slc = non-temporal (see SM_ST_AUX, sm_device.h)
 #endif
-#ifndef SM_COST_SPLIT
-#define SM_COST_SPLIT 1
-#endif
-#ifndef SM_COST_ONE_PAIR
-#define SM_COST_ONE_PAIR 1   // D <= 64: two focus pixels per trip (profiles/r5t/ab_one.log)
-#endif
-#ifndef SM_COST_ONE_FAST
-#define SM_COST_ONE_FAST 1   // D <= 64: FAST elements too, with two pixels per trip (Teddy x16 0.169 -> 0.166 ms)
-#endif
 #ifndef SM_COST_UNROLL
 #define SM_COST_UNROLL 1
-#endif
-#ifndef SM_COST_ND
-#define SM_COST_ND 1   // D = 128 / 192 / 256: element loop unrolled at compile time (k_cost<..., ND>)
 #endif
 // Pixels of a row segment per block (at most; launch_cost splits a row into equal segments of
 // at most this many): D <= 64 amortises the P + D - 1 moving-pixel staging over up to 240 pixels
@@ -875,9 +816,6 @@ __host__ __device__ constexpr int cost_rec_u4() { return CW <= 2 ? 1 : 2; }
 // The select-free elements (NOSEL = censusGrad with >= 3 census words and OORZ), their FAST form,
 // the sentinel record of an out-of-range candidate and the LDS table reads are in sm_cost_elem.h,
 // shared with the CBCA sweep that computes its own costs (k_cbca_hsc, sm_cbca.hip).
-#ifndef SM_COST_FAST
-#define SM_COST_FAST 1
-#endif
 
 // ND > 0: D == 64 * ND, the element loop fully unrolled (LDS and store offsets become immediates;
 // no loop counter, compare or pointer increments: 35 -> ~29 VALU per element at D = 256)
@@ -910,13 +848,11 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
     constexpr bool ADM = METHOD == SM_M_AD || METHOD == SM_M_AD_CENSUS;
     uint4* mrec = (uint4*)cs_raw;                                // [(P + D - 1) * RW]
     ulonglong2* fcode = (ulonglong2*)(mrec + RW * (COST_P + D - 1));  // [P]
-    // SM_COST_SPLIT: records of 2 uint4 (CW = 3, 4) live as two planes, so a lane's record
-    // reads are 16-byte (plane A) and 8 / 16-byte (plane B) strided instead of 32-byte strided
-    // (half the LDS banks per pass: 2-way conflicts on every element)
-    constexpr bool SPLIT = SM_COST_SPLIT && RW == 2;
-    uint4* mrecB4 = mrec + (COST_P + D - 1);                     // plane B (SPLIT), CW = 4
-    uint2* mrecB2 = (uint2*)mrecB4;                              // plane B (SPLIT), CW = 3
-    auto recA = [&](int i) -> uint4& { return SPLIT ? mrec[i] : mrec[RW * i]; };
+    // records of 2 uint4 (CW = 3, 4) live as two planes, so a lane's record reads are 16-byte
+    // (plane A, mrec) and 8 / 16-byte (plane B) strided instead of 32-byte strided (half the LDS
+    // banks per pass: 2-way conflicts on every element)
+    uint4* mrecB4 = mrec + (COST_P + D - 1);                     // plane B, CW = 4
+    uint2* mrecB2 = (uint2*)mrecB4;                              // plane B, CW = 3
     float* fgx = (float*)(fcode + COST_P);                       // [P]
     float* fgy = fgx + COST_P;
     float* fwa = fgy + COST_P;                                   // adaptive weight a (1 if off)
@@ -976,17 +912,14 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
             bias = (uint32_t)icd;
         }
         if (CW == 4) {
-            recA(i) = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), (uint32_t)c.y, (uint32_t)(c.y >> 32));
-            if (SPLIT) mrecB4[i] = make_uint4(w2, w3, bias, 0);
-            else mrec[2 * i + 1] = make_uint4(w2, w3, bias, 0);
+            mrec[i] = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), (uint32_t)c.y, (uint32_t)(c.y >> 32));
+            mrecB4[i] = make_uint4(w2, w3, bias, 0);
         } else if (CW == 3 && NOSEL) {   // {census words, bias} and {gx, gy} (one 8-byte read)
-            recA(i) = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), (uint32_t)c.y, bias);
-            if (SPLIT) mrecB2[i] = make_uint2(w2, w3);
-            else mrec[2 * i + 1] = make_uint4(w2, w3, 0, 0);
+            mrec[i] = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), (uint32_t)c.y, bias);
+            mrecB2[i] = make_uint2(w2, w3);
         } else if (CW == 3) {
-            recA(i) = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), (uint32_t)c.y, w2);
-            if (SPLIT) mrecB2[i] = make_uint2(w3, bias);
-            else mrec[2 * i + 1] = make_uint4(w3, bias, 0, 0);
+            mrec[i] = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), (uint32_t)c.y, w2);
+            mrecB2[i] = make_uint2(w3, bias);
         } else {
             mrec[i] = make_uint4((uint32_t)c.x, (uint32_t)(c.x >> 32), w2, w3);
         }
@@ -1021,14 +954,14 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
             constexpr bool FAST = decltype(fastc)::value;
             const int q = mi + mbase;
             if constexpr (NOSEL) {
-                const uint4 r0 = recA(mi);
+                const uint4 r0 = mrec[mi];
                 uint32_t pc;
                 uint2 gw;
                 if constexpr (CW == 3) {
-                    gw = SPLIT ? mrecB2[mi] : *(const uint2*)&mrec[RW * mi + 1];
+                    gw = mrecB2[mi];
                     pc = r0.w;                         // icd for out-of-range candidates, else 0
                 } else {
-                    const uint4 r1 = SPLIT ? mrecB4[mi] : mrec[RW * mi + 1];
+                    const uint4 r1 = mrecB4[mi];
                     pc = r1.z;
                     gw = make_uint2(r1.x, r1.y);
                 }
@@ -1040,7 +973,7 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
                 return;
             }
             const bool oor = (unsigned)q >= (unsigned)W;
-            const uint4 r0 = recA(mi);
+            const uint4 r0 = mrec[mi];
             uint32_t w2 = r0.z, w3 = r0.w;
             uint32_t pc = 0;
             if (CEN) {
@@ -1050,9 +983,9 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
             }
             if (CW == 3) {
                 w2 = r0.w;
-                w3 = SPLIT ? mrecB2[mi].x : ((const uint32_t*)mrec)[4 * (RW * mi + 1)];
+                w3 = mrecB2[mi].x;
             } else if (CW == 4) {
-                const uint4 r1 = SPLIT ? mrecB4[mi] : mrec[RW * mi + 1];
+                const uint4 r1 = mrecB4[mi];
                 w2 = r1.x;
                 w3 = r1.y;
             }
@@ -1115,11 +1048,13 @@ __global__ __launch_bounds__(256) void k_cost(const CostArgs a) {
     // FAST (see COST_OOR_GRAD): a wave-uniform choice per focus pixel; the general elements are
     // valid for every pixel.  (Two pixels per trip: no fewer instructions per element.)
     // (for ONE only with two pixels per trip: one element per lane and pixel leaves the table
-    // read's latency exposed, Teddy x16 0.164 -> 0.178 ms, profiles/r5n/ab3_teddy.log)
-    constexpr bool FASTOK = SM_COST_FAST && NOSEL && LAM1 && (!ONE || SM_COST_ONE_FAST);
+    // read's latency exposed, Teddy x16 0.164 -> 0.178 ms, profiles/r5n/ab3_teddy.log; with them
+    // 0.169 -> 0.166 ms)
+    constexpr bool FASTOK = NOSEL && LAM1;
     int pl = wy;
-    if constexpr (ONE && SM_COST_ONE_PAIR) {
+    if constexpr (ONE) {
         // D <= 64: pixels pl and pl + 4 per trip, two independent elements per lane
+        // (profiles/r5t/ab_one.log)
         for (; pl + 4 < np; pl += 8) {
             const int u = u0 + pl;
             if (FASTOK && fast_rows && u > 0 && u + 4 < W - 1) {
@@ -1231,14 +1166,12 @@ template <int METHOD, bool LAM1, int CW, bool OORZ>
 static void launch_cost_z(const CostArgs& a, dim3 grid, dim3 block, size_t shm, hipStream_t st) {
     if (a.D <= 64)
         hipLaunchKernelGGL((k_cost<METHOD, LAM1, CW, true, OORZ>), grid, block, shm, st, a);
-#if SM_COST_ND
-    else if (a.D == 256)
+    else if (a.D == 256)   // D = 128 / 192 / 256: the element loop unrolled at compile time (ND)
         hipLaunchKernelGGL((k_cost<METHOD, LAM1, CW, false, OORZ, 4>), grid, block, shm, st, a);
     else if (a.D == 192)
         hipLaunchKernelGGL((k_cost<METHOD, LAM1, CW, false, OORZ, 3>), grid, block, shm, st, a);
     else if (a.D == 128)
         hipLaunchKernelGGL((k_cost<METHOD, LAM1, CW, false, OORZ, 2>), grid, block, shm, st, a);
-#endif
     else
         hipLaunchKernelGGL((k_cost<METHOD, LAM1, CW, false, OORZ>), grid, block, shm, st, a);
 }

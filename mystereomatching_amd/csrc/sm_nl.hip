@@ -28,9 +28,6 @@
 #ifndef SM_NL_BLOCK
 #define SM_NL_BLOCK 4   // path nodes whose loads are issued together (tuning)
 #endif
-#ifndef SM_NL_PIPE
-#define SM_NL_PIPE 1    // issue the next block's loads before this block's arithmetic (tuning)
-#endif
 #ifndef SM_NL_BLOCK_SHORT
 #define SM_NL_BLOCK_SHORT 2      // ... in rounds of at least SM_NL_SHORT_UNITS (path, chunk) units
 #endif
@@ -125,8 +122,8 @@ __device__ __forceinline__ int nl_child(int x, int meta, int j, int W) {
 
 // Up pass over the paths order_up[lo, ...): bottom -> top.  A path is walked in blocks of K nodes:
 // every load of a block (the node's cost, its other children's finished sums, the edge weights)
-// is issued before the block's sequential arithmetic, and with SM_NL_PIPE the next block's loads
-// are issued before this block's arithmetic, so a long path pays a memory latency per K nodes or
+// is issued before the block's sequential arithmetic, and the next block's loads are issued
+// before this block's arithmetic, so a long path pays a memory latency per K nodes or
 // less instead of a chain of dependent loads per node.  The branches around the loads are uniform
 // (scalar); the records themselves are read past the path's end (the next path or zero padding,
 // NL_REC_PAD) so that a block's records arrive in one go.
@@ -221,7 +218,6 @@ __global__ __launch_bounds__(64 * SM_NL_WAVES) void k_nl_up(const NlArgs a, cons
     const int4* __restrict__ R = rec + a.chain_start[ci];
     const int len = a.chain_len[ci];
     double carry = 0.0, carry_o = 0.0;
-#if SM_NL_PIPE
     NlUpBlock<K> X, Y;
     nl_up_load(X, a, R, 0, len, P, d);
     for (int b = 0; b < len; b += 2 * K) {
@@ -233,14 +229,6 @@ __global__ __launch_bounds__(64 * SM_NL_WAVES) void k_nl_up(const NlArgs a, cons
         nl_up_weigh(Y, table);
         nl_up_compute(Y, a, b + K, len, P, d, carry, carry_o);
     }
-#else
-    for (int b = 0; b < len; b += K) {
-        NlUpBlock<K> X;
-        nl_up_load(X, a, R, b, len, P, d);
-        nl_up_weigh(X, table);
-        nl_up_compute(X, a, b, len, P, d, carry, carry_o);
-    }
-#endif
 }
 
 // Down pass over the paths order_down[lo, ...): top -> bottom, blocked like the up pass; writes
@@ -322,7 +310,6 @@ __global__ __launch_bounds__(64 * SM_NL_WAVES) void k_nl_down(const NlArgs a, co
     // the top's parent is on a path finished in an earlier round (or the top is the root)
     double carry = top.w == top.x ? 0.0 : a.val[(size_t)top.w * P + d];
     double carry_o = top.w == top.x ? 0.0 : a.ofin[top.w];
-#if SM_NL_PIPE
     NlDownBlock<K> X, Y;
     nl_down_load(X, a, R, len - 1, P, d);
     for (int b = len - 1; b >= 0; b -= 2 * K) {
@@ -332,13 +319,6 @@ __global__ __launch_bounds__(64 * SM_NL_WAVES) void k_nl_down(const NlArgs a, co
         nl_down_load(X, a, R, b - 2 * K, P, d);
         nl_down_compute(Y, a, table, b - K, P, d, carry, carry_o);
     }
-#else
-    for (int b = len - 1; b >= 0; b -= K) {
-        NlDownBlock<K> X;
-        nl_down_load(X, a, R, b, P, d);
-        nl_down_compute(X, a, table, b, P, d, carry, carry_o);
-    }
-#endif
 }
 
 

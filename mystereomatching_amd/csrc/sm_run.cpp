@@ -1,6 +1,5 @@
 // sm_run.cpp — the batch path: the stream schedule (apply_schedule, sm_set_schedule), sm_run's groups and
 // pipeline, the volume placement trials, and the uploads and downloads that feed and drain it.
-// Compile-time A/B switches of this file: SM_FUSE_SOLVE_ALL, SM_STAGGER_STAGE, SM_UP_EARLY.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -9,16 +8,6 @@
 #include <thread>
 
 #include "sm_ctx.h"
-
-#ifndef SM_FUSE_SOLVE_ALL
-#define SM_FUSE_SOLVE_ALL 1   // sm_run: SolveAll's scaling in the GF / NL output stores (tuning switch)
-#endif
-#ifndef SM_STAGGER_STAGE
-#define SM_STAGGER_STAGE 1   // 0: CBCA groups also start after the previous group's whole CBCA (A/B)
-#endif
-#ifndef SM_UP_EARLY
-#define SM_UP_EARLY 1   // async uploads into a pipelined context wait for the inputs' last reader, not the group's end
-#endif
 
 // sm_params.num_streams / sub_batch -> the schedule sm_run follows (sm_create, sm_set_schedule).
 // num_streams 0 (auto): two streams with CBCA at volumes >= 256 MiB per pair, where the next
@@ -113,13 +102,13 @@ static sm_status run_group(sm_ctx* c, Group G, int k, const Schedule& S) {
         if ((s = run_prep(c, G))) return s;
         if ((s = run_cost(c, 0, G))) return s;
         if (right_view(c->p) && (s = run_cost(c, 1, G))) return s;
-        if ((s = run_other_agg(c, G, SM_FUSE_SOLVE_ALL, S.w))) return s;   // SolveAll fused into GF / NL
+        if ((s = run_other_agg(c, G, true, S.w))) return s;   // SolveAll fused into the GF / NL output stores
     }
     // the group's input images are read by prep and the cost volume only (CBCA + SGM, no refinement:
     // the pipelined form): the next call's async upload may overwrite them once ev_in[k] is recorded --
     // here; or, where a fused first CBCA sweep reads the gray images and census codes itself, by run_cbca
     // after the last view's first sweep
-    if (S.piped && SM_UP_EARLY) {
+    if (S.piped) {
         if ((s = use_event(c, c->ev_in[k]))) return s;
         if (cost_scan_fused(c, 0)) G.in_ev = c->ev_in[k];
         else HIP_TRY(c, hipEventRecord(c->ev_in[k], G.st));
@@ -129,7 +118,7 @@ static sm_status run_group(sm_ctx* c, Group G, int k, const Schedule& S) {
     for (int v = 0; v < n_views(c->p) && !S.nl_pipe; v++) {
         if (c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0)
             s = run_cbca(c, v, true, S.w, G);   // SolveAll fused into the last pass
-        else if (!SM_FUSE_SOLVE_ALL || !agg_scale_fused(c->p, v))
+        else if (!agg_scale_fused(c->p, v))
             s = run_scale(c, v, S.w, G);      // (GF, FIF, AWS, BF, GFNL and NL's vm[0]: fused above)
         if (s) return s;
     }
@@ -185,11 +174,11 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     Schedule S;
     S.w = (float)(1. / (double)m);
     S.piped = c->pipelined && ns == 2 && n >= 2 && (n + g - 1) / g == 2;
-    S.early = !S.piped && SM_STAGGER_STAGE == 1 && c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0;
+    S.early = !S.piped && c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0;
     // (a different split of the pairs would let the groups of two calls share a pair: join first)
     if ((!S.piped || g != c->pipe_g) && (s = join_all(c))) return s;
     S.start = !(S.piped && c->pipe_live);
-    S.nl_pipe = c->nl_pipe && g >= n && ns == 1 && SM_FUSE_SOLVE_ALL;
+    S.nl_pipe = c->nl_pipe && g >= n && ns == 1;
     if (ns > 1 && S.start) {   // the side streams start after everything queued so far on the main stream
         if ((s = use_event(c, c->ev_start))) return s;
         HIP_TRY(c, hipEventRecord(c->ev_start, c->st));
@@ -368,7 +357,7 @@ sm_status sm_upload_batch_async(sm_ctx* c, int32_t n, const uint8_t* lbgr, const
     // (ev_in, recorded after its cost volume -- after its first CBCA sweep where that sweep computes
     // the costs from the gray images itself, run_cbca), so they overlap that group's CBCA and SGM; the
     // group's next kernels wait for its copies (ev_up)
-    const bool early = split && SM_UP_EARLY && c->ev_in[0] && c->ev_in[1];
+    const bool early = split && c->ev_in[0] && c->ev_in[1];
     const hipStream_t ust = nullptr;
     for (int grp = 0; early && grp < 2; grp++) {
         HIP_TRY(c, hipStreamWaitEvent(ust, c->ev_in[grp], 0));

@@ -631,27 +631,21 @@ static int rows_kv(const SgmArgs& a, int mode) {
 // are k_sgm's diagonals of the first path (W + H - 1 of them, 1 .. min(H, W) steps; checkpoint
 // slots strided by the longest), segments of SM_SGM_CK_SD steps.
 // ---------------------------------------------------------------------------------------
-#ifndef SM_SGM_CK
-#define SM_SGM_CK 1
-#endif
 #ifndef SM_SGM_CK_S
 #define SM_SGM_CK_S 8        // segment steps (layouts with 4 disparities per lane)
 #endif
 #ifndef SM_SGM_CK_S2
 #define SM_SGM_CK_S2 4       // segment steps with 8 disparities per lane (D in (64, 128])
 #endif
-
-#ifndef SM_SGM_CK_DIAG
-#define SM_SGM_CK_DIAG 1     // 8 paths, 128 < D <= 256: the diagonal pair (4, 6) checkpointed too
-#endif
 #ifndef SM_SGM_CK_SD
 #define SM_SGM_CK_SD 4       // segment steps of the diagonal pair (its pass B also holds L5's segment)
 #endif
 
-bool sgm_ck_ok(int D, int paths) { return SM_SGM_CK && (paths == 4 || paths == 8) && D <= 256 && D % 4 == 0; }
+bool sgm_ck_ok(int D, int paths) { return (paths == 4 || paths == 8) && D <= 256 && D % 4 == 0; }
 static int ck_kv(int D) { return D > SM_SGM_VEC_MIN_D ? 0 : ((D + 15) / 16 + 3) / 4; }   // 0: one line per wave
 int sgm_ck_seg(int D) { return ck_kv(D) == 2 ? SM_SGM_CK_S2 : SM_SGM_CK_S; }
-bool sgm_ck_diag_ok(int D, int paths) { return SM_SGM_CK_DIAG && paths == 8 && sgm_ck_ok(D, paths) && ck_kv(D) == 0; }
+// (8 paths, 128 < D <= 256: the diagonal pair (4, 6) checkpointed too)
+bool sgm_ck_diag_ok(int D, int paths) { return paths == 8 && sgm_ck_ok(D, paths) && ck_kv(D) == 0; }
 int sgm_ck_diag_seg() { return SM_SGM_CK_SD; }
 
 template <int KV, bool ROWS, bool FULL, bool SG>

@@ -22,10 +22,6 @@
 #include "sm_device.h"
 #include "sm_kernels.h"
 
-#ifndef SM_SO_LDS_TRACE
-#define SM_SO_LDS_TRACE 1
-#endif
-
 namespace sm {
 
 namespace {
@@ -244,7 +240,7 @@ void launch_so(const SoArgs& a, hipStream_t st) {
     const int k = (a.D + 63) / 64;
     const int kk = k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)));
     const size_t shm = 4 * so_lds_words(a.W, kk) * 8;
-    const bool lt = shm <= 64 * 1024 && SM_SO_LDS_TRACE;
+    const bool lt = shm <= 64 * 1024;   // the row's trace in LDS when it fits, else in global memory
     const size_t sh = lt ? shm : 0;
 #define SM_SO_LAUNCH(KV)                                                              \
     do {                                                                              \

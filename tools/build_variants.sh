@@ -3,8 +3,6 @@
 # switches (default sm_cbca.hip; SRC=sm_kernels, SRC=sm_sgm, SRC=sm_run (.cpp), ... for the others), for same-box A/B
 # runs on one GPU box (tools/ab_inproc.py; tools/abvar/ travels with gpurun -- delete it after the A/B
 # so that later pushes, the driver's included, do not carry it).
-# The host files' switches: SM_FUSE_SOLVE_ALL, SM_STAGGER_STAGE and SM_UP_EARLY are read by sm_run.cpp
-# (SRC=sm_run), SM_NL_PIPE by sm_capi.cpp (SRC=sm_capi).
 # The library's objects are the Makefile's (its list-kernel-objects and list-host-sources targets).
 # usage: [SRC=sm_cbca] tools/build_variants.sh NAME "-DSWITCH=value ..." [NAME2 "DEFS2" ...]
 set -e

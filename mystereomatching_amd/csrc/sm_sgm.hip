@@ -71,6 +71,18 @@ __device__ __forceinline__ float dpp_shl1(float v) {  // lane l <- lane l+1; lan
                                                                  __builtin_bit_cast(int, v), DPP_WAVE_SHL1, 0xF, 0xF, false));
 }
 
+// SIGNED only (a no-op otherwise).  The reference's minima are std::min(a, b) = (b < a) ? b : a,
+// which keeps a NaN first operand: with an all-NaN previous column minC is NaN, S1 .. S3 are NaN
+// and min4 returns NaN at every disparity, so a NaN pixel poisons its path to the end, while
+// v_min_f32 drops the NaN operands and would return P2.  NaN reaches a guided-filter volume per
+// pixel (through the guide's inverse covariance, the same for every disparity), so a column of
+// path costs is all NaN or all finite and S1 = Lp[d] - m is NaN exactly where the reference's
+// result is: its NaN is handed on.
+template <bool SG>
+__device__ __forceinline__ float keep_nan(float S1, float Lk) {
+    return (SG && S1 != S1) ? S1 : Lk;
+}
+
 template <int K, int T>
 struct SgmTile {
     float c[T][K];
@@ -203,11 +215,21 @@ __global__ __launch_bounds__(256) void k_sgm(const SgmArgs a) {
 
     // All path costs are >= +0 (C >= 0; Lp - m >= 0; Lp[d +/- 1] + (P1 - m) >= 0 because
     // fl(P1 - m) >= -m; P2 > 0), so every min below is an exact unsigned min on the bit patterns.
-    // SIGNED (guided-filter costs, which can be negative but are never -0 or NaN, nor are the
-    // sums of them): v_min_f32 minima, which then equal the reference's std::min exactly.
+    // SIGNED (guided-filter costs of either sign): v_min_f32 minima, which equal the reference's
+    // std::min on finite operands (up to the sign of a zero when +0 meets -0, which compare
+    // equal in every later test and differ in a sum only if every addend is a zero).  The
+    // guided filter's volume can also be NaN: on a grey image stored as colour with high contrast
+    // the 3 x 3 covariance is singular in float (eps is absorbed), the inverse is 0 * inf and the
+    // box sums spread NaN over the pixels in reach (all of a small image).  A NaN pixel has NaN
+    // at every disparity; its path costs are NaN (C + anything), and so are those of every later
+    // pixel of the path (keep_nan above), as in the reference.  The strict `>` / `< FLT_MAX`
+    // tests of the arg-min below then give -1 like gen_dispFromVm (cpp:3940-3964).  Guaranteed:
+    // volumes whose pixels are finite or NaN at every disparity; a column that mixes NaN and
+    // finite costs is not (the reference's result there depends on std::min's operand order).
     // Out-of-range neighbours (d - 1 < 0, d + 1 >= D) hold FLT_MAX from the DPP shift's bound
-    // value or the padded lanes; FLT_MAX + (P1 - m) never undercuts P2 <= 3, so those terms
-    // cannot win the min and need no separate select.
+    // value or the padded lanes; FLT_MAX + (P1 - m) rounds back to FLT_MAX for every |P1 - m|
+    // below 2^103 (half an ulp of FLT_MAX), so those terms cannot undercut any finite P2 -- also
+    // P2 = 100 or P1 > P2 -- and need no separate select.
     auto step = [&](const SgmTile<K, T>& t, int s, int j, bool start) {
         float L[K];
         if (start) {
@@ -232,7 +254,7 @@ __global__ __launch_bounds__(256) void k_sgm(const SgmArgs a) {
                 const float S2 = prev + P1m;
                 const float S3 = next + P1m;
                 const float mm = SG ? fminf(fminf(S1, S2), fminf(S3, P2)) : fmin_pos(fmin_pos(S1, S2), fmin_pos(S3, P2));
-                const float Lk = t.c[s][k] + mm;
+                const float Lk = keep_nan<SG>(S1, t.c[s][k] + mm);
                 L[k] = (FULL || val[k]) ? Lk : FLT_MAX;
             }
         }
@@ -256,7 +278,8 @@ __global__ __launch_bounds__(256) void k_sgm(const SgmArgs a) {
             // (padded lanes hold FLT_MAX and only match when every cost is FLT_MAX -> -1)
             const float wm = SG ? wave_min(bm) : wave_min_pos(bm);
             const uint64_t hit = __ballot(bm == wm);
-            const int widx = __builtin_amdgcn_readlane(bi, (int)__builtin_ctzll(hit));
+            // SIGNED: an all-NaN column matches nowhere; lane 0 stands in (the result is -1 then)
+            const int widx = __builtin_amdgcn_readlane(bi, (SG && !hit) ? 0 : (int)__builtin_ctzll(hit));
             const int dsel = (wm < FLT_MAX) ? widx : -1;
             dacc = (lane == s) ? dsel : dacc;
         } else {
@@ -439,7 +462,7 @@ __global__ __launch_bounds__(256) void k_sgm_rows(const SgmArgs a) {
                 const float S2 = prev + P1m;
                 const float S3 = next + P1m;
                 const float mm = mn(mn(S1, S2), mn(S3, P2));
-                const float Lk = t.c[s][k] + mm;
+                const float Lk = keep_nan<SG>(S1, t.c[s][k] + mm);
                 L[k] = cval[k / 4] ? Lk : FLT_MAX;
             }
         }
@@ -481,7 +504,8 @@ __global__ __launch_bounds__(256) void k_sgm_rows(const SgmArgs a) {
                 const float wm = rmin(bm);
                 const uint64_t hit = __ballot(bm == wm);
                 const uint32_t rmask = (uint32_t)(hit >> (row * 16)) & 0xffffu;
-                const int src = row * 16 + __builtin_ctz(rmask);
+                // SIGNED: an all-NaN row matches nowhere; its lane 0 stands in (the result is -1 then)
+                const int src = row * 16 + ((SG && !rmask) ? 0 : __builtin_ctz(rmask));
                 const int widx = __builtin_amdgcn_ds_bpermute(src * 4, bi);
                 const int dsel = (wm < FLT_MAX) ? widx : -1;
                 dacc = (l16 == s) ? dsel : dacc;
@@ -681,7 +705,7 @@ struct CkStep {
             const float S2 = prev + P1m;
             const float S3 = next + P1m;
             const float mm = mn(mn(S1, S2), mn(S3, P2));
-            const float Lk = c[k] + mm;
+            const float Lk = keep_nan<SG>(S1, c[k] + mm);
             L[k] = (FULL || cv[k / 4]) ? Lk : FLT_MAX;
         }
     }
@@ -887,12 +911,12 @@ __global__ __launch_bounds__(256) void k_sgm_ck(const SgmArgs a) {
                 }
             const float wm = st.line_min(bm);
             const uint64_t hit = __ballot(bm == wm);
-            int widx;
+            int widx;   // SIGNED: an all-NaN line matches nowhere; its lane 0 stands in (the result is -1 then)
             if (ROWS) {
                 const uint32_t rmask = (uint32_t)(hit >> (row * 16)) & 0xffffu;
-                widx = __builtin_amdgcn_ds_bpermute((row * 16 + __builtin_ctz(rmask)) * 4, bi);
+                widx = __builtin_amdgcn_ds_bpermute((row * 16 + ((SG && !rmask) ? 0 : __builtin_ctz(rmask))) * 4, bi);
             } else {
-                widx = __builtin_amdgcn_readlane(bi, (int)__builtin_ctzll(hit));
+                widx = __builtin_amdgcn_readlane(bi, (SG && !hit) ? 0 : (int)__builtin_ctzll(hit));
             }
             const int dsel = (wm < FLT_MAX) ? widx : -1;
             dacc = (ll == s) ? dsel : dacc;

@@ -198,7 +198,9 @@ sm_status validate(const sm_params& p, std::string& why) {
     if (!(p.lam_cen > 0) || !(p.lam_g > 0) || !(p.lam_ad > 0) || !(p.lam_cen_adc > 0))
         return bad("fusion lambdas must be > 0");
     // -0.0 passes `>= 0` but its bit pattern 0x80000000 ranks above every positive cost in those
-    // unsigned minima (the reference's std::min would treat it as 0), so it is rejected as well
+    // unsigned minima (the reference's std::min would treat it as 0), so it is rejected as well.
+    // (GF, GFNL and inexact BF run SGM's float-minimum variants instead, which take costs of either
+    // sign and volumes whose pixels are NaN at every disparity: sm_sgm.hip, keep_nan.)
     if (!nonneg(p.grad_trunc) || !nonneg(p.ad_trunc_adc) || !nonneg(p.ad_trunc_ad)) return bad("truncations must be >= +0");
     if (!nonneg(p.sgm_p1) || !nonneg(p.sgm_p2) || p.sgm_redu_coeff < 0) return bad("SGM penalties must be >= +0");
     if (p.do_refine) {

@@ -41,6 +41,9 @@
  *                          backgroundInterpolateCore cpp:7011-7043, subpixelEnhancement cpp:6138-6167)
  *   sm_get_pkr_mask    <- member PKR_Err_Mask as calPKR leaves it (cpp:1380)
  *   sm_get_subpixel / sm_download_subpixel <- refine()'s local SE after medianBlur(SE, SE, 3) (cpp:1484-1490)
+ *   sm_refine_da_config <- static switch Do_discontinuityAdjust (h:78), the literals of cpp:6063-6064
+ *                         (discontinuityAdjust cpp:6057-6136)
+ *   sm_get_da_edges    <- discontinuityAdjust's local disp_E after Canny (cpp:6064)
  *   sm_get_volume / sm_set_volume <- public member vm[view]       stereoMatching.h:2720
  *   sm_get_arms        <- public member HVL[view]                    stereoMatching.h:2717
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
@@ -442,8 +445,8 @@ typedef enum sm_se_mode {
  * that is not finite, disp_pkr outside [-32768, -1], bg_ipl_depth outside [0, 32767], se_mode outside {0, 1},
  * do_pkr with num_disparities < 2 (the reference's second search writes slot -1), and do_pkr or do_subpixel with
  * optimization "so" (the reference's so rewrites vm in place, cpp:6299; this back end keeps a trace instead);
- * the arguments are checked without a device.  Not built: Do_WM (reads a mask the shipped LR check never
- * writes), Do_discontinuityAdjust and Do_cbbi (need an OpenCV the reference does not pin). */
+ * the arguments are checked without a device.  Do_discontinuityAdjust is built (sm_refine_da_config).  Not built:
+ * Do_WM (reads a mask the shipped LR check never writes) and Do_cbbi (needs floodFill and theRNG()). */
 SM_API sm_status sm_refine_ext_config(sm_ctx* ctx, int32_t do_pkr, float pkr_ratio, int32_t disp_pkr, int32_t do_bg_ipol,
                                       int32_t bg_ipl_depth, int32_t do_subpixel, int32_t se_mode);
 /* Pair 0's PKR_Err_Mask / float map SE of the last sm_refine / sm_run with the stage on: rows x cols bytes /
@@ -452,6 +455,31 @@ SM_API sm_status sm_get_pkr_mask(sm_ctx* ctx, uint8_t* dst);
 SM_API sm_status sm_get_subpixel(sm_ctx* ctx, float* dst);
 /* The float maps of the first n pairs, [n][H][W], to a host or device pointer (synchronous). */
 SM_API sm_status sm_download_subpixel(sm_ctx* ctx, int32_t n, float* dst);
+
+/* refine()'s discontinuity adjustment (Do_discontinuityAdjust, h:78; discontinuityAdjust, cpp:6057-6136), "DA": per
+ * pair on DP[0] and vm[0] as dispOptimize left it, after BGIpol and before the sub-pixel map and the last median
+ * (cpp:1454-1497).  DP[0] clamped to 8 bits -> equalizeHist -> GaussianBlur(3 x 3, sigma 4) -> Canny(canny_low,
+ * canny_high, 3, L1) gives an edge map; then, in raster order and IN PLACE over the interior, an edge pixel with a
+ * direction (cpp:6079-6098) and DP >= 0 takes the disparity of the neighbour on either side of the edge whose cost
+ * at its own disparity is lower (first side on cost >= 0, second side on cost != -1).  The three OpenCV calls are
+ * restated in integers (the reference pins no OpenCV): the blur in OpenCV's 8.8 fixed-point form with
+ * the taps (blur_side, blur_centre, blur_side) = (84, 87, 84), which are arguments so that a build whose kernel
+ * sums to 256 can be matched.  One deviation: a disparity >= num_disparities in the map (possible only through
+ * sm_set_disp) reads its cost as -1 where the reference reads outside the volume.  The imwrite of the edge image
+ * is not reproduced.  rows < 3 or cols < 3 changes nothing.
+ * Not sm_params fields (the struct keeps its size): off by default (20, 60, 84, 87 are the reference's values),
+ * takes effect from the next sm_disp_optimize / sm_refine / sm_run.  With "sgm", SGM writes its path sum into
+ * vm[0] for the stage to read, as for do_pkr; switched on after sm_disp_optimize ran without it, sm_refine returns
+ * SM_ESTATE.  The maps are the same for every schedule; no launch count depends on the data and nothing is read
+ * back.  The scratch is allocated on the first enabling call (batch_capacity pairs).  SM_EINVAL, with the argument
+ * named in sm_last_error, on a context without do_refine, with optimization "so", for a threshold outside
+ * [0, 32767] (given in the wrong order they are swapped), a negative tap or 2 * blur_side + blur_centre > 256; the
+ * arguments are checked without a device. */
+SM_API sm_status sm_refine_da_config(sm_ctx* ctx, int32_t on, int32_t canny_low, int32_t canny_high, int32_t blur_side,
+                                     int32_t blur_centre);
+/* Pair 0's edge map (0 / 255) of the last sm_refine / sm_run with the stage on: rows x cols bytes.  SM_ESTATE
+ * before that. */
+SM_API sm_status sm_get_da_edges(sm_ctx* ctx, uint8_t* dst);
 
 /* Diagnostics used by the parity tests. */
 /* CBCA's double window: pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where
@@ -463,6 +491,16 @@ SM_API sm_status sm_get_cbca_area(sm_ctx* ctx, int32_t view, int32_t* dst);
 /* "GFNL": pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where the variance
  * is below the threshold, i.e. where vm[0] is NL's value alone). */
 SM_API sm_status sm_get_gfnl_mask(sm_ctx* ctx, uint8_t* dst);
+/* The discontinuity adjustment's image stages on a supplied rows x cols 8-bit image, with sm_refine_da_config's
+ * thresholds and taps: the image enters at first_stage 0 (equalizeHist), 1 (GaussianBlur) or 2 (Canny); out_eq,
+ * out_blur and out_edges receive the stages' outputs (rows x cols bytes each).  NULL outputs are skipped, and so
+ * are the outputs of stages before first_stage.  Uses pair 0's scratch: sm_get_da_edges gives SM_ESTATE after it
+ * until the next refine. */
+SM_API sm_status sm_da_run_image(sm_ctx* ctx, const uint8_t* src_u8, int32_t first_stage, uint8_t* out_eq,
+                                 uint8_t* out_blur, uint8_t* out_edges);
+/* The following sm_refine / sm_run calls use this rows x cols edge map (non-zero = edge) for every pair instead of
+ * running the image stages; NULL returns to Canny's. */
+SM_API sm_status sm_set_da_edges(sm_ctx* ctx, const uint8_t* edges);
 /* "AWS": OpenCV's 8-bit BGR2Lab on the host (no device needed) with the tables the kernels use:
  * npix packed BGR pixels -> npix packed (L, a, b); and the H x W x 3 plane the device computed for
  * pair 0's image `view` in the last sm_cost_calculate / sm_run. */

@@ -342,6 +342,11 @@ class StereoMatching {
     // converted back, truncating toward zero), true keeps the float
     inline static bool SE_FLOAT = false;
     inline static float pkr_ratio = 0.1f;          // calPKR's local ratio_PKR (cpp:4093)
+    // refine()'s discontinuity adjustment (h:78; sm_refine_da_config): equalizeHist, GaussianBlur and Canny on DP[0]
+    // as 8 bits, then the raster-order pass of cpp:6069-6135; refine() leaves the edge map in DA_Edge.  The
+    // thresholds and the blur's 8.8 fixed-point taps are the literals of cpp:6063-6064 in the restated form
+    inline static bool Do_discontinuityAdjust = false;
+    inline static int da_canny_low = 20, da_canny_high = 60, da_blur_side = 84, da_blur_centre = 87;
     inline static bool Do_properIpol = true;       // h:76
     inline static bool Do_lastMedianBlur = true;   // h:80
     // `#define MY_GUIDE` (h:38, commented out in the shipped build) as a switch: false = GF runs
@@ -446,6 +451,10 @@ class StereoMatching {
             PKR_Err_Mask.create(h_, w_, CV_8U);
             check(sm_get_pkr_mask(ctx_, PKR_Err_Mask.ptr<uint8_t>()), "PKR_Err_Mask");
         }
+        if (da_on_) {
+            DA_Edge.create(h_, w_, CV_8U);
+            check(sm_get_da_edges(ctx_, DA_Edge.ptr<uint8_t>()), "DA_Edge");
+        }
         if (se_on_) {
             SE.create(h_, w_, CV_32F);
             check(sm_get_subpixel(ctx_, SE.ptr<float>()), "SE");
@@ -505,6 +514,7 @@ class StereoMatching {
     Mat DT;           // ground truth (cpp:2072)
     Mat SE;           // float H x W: refine()'s local SE after its median (cpp:1484-1490), with Do_subpixelEnhancement
     Mat PKR_Err_Mask; // uint8 H x W: calPKR's mask (cpp:1380), with Do_calPKR
+    Mat DA_Edge;      // uint8 H x W: discontinuityAdjust's edge map (cpp:6064), with Do_discontinuityAdjust
     Mat I_mask[3];    // nonocc, all, disc (cpp:2073-2075)
     Parameters param_;
     int h_, w_, d_;
@@ -512,7 +522,7 @@ class StereoMatching {
 
    private:
     bool refine_on_ = false, csv_open_ = false;
-    bool pkr_on_ = false, se_on_ = false;
+    bool pkr_on_ = false, se_on_ = false, da_on_ = false;
     std::ostringstream csv_;
     std::vector<std::string> times_;
 
@@ -606,6 +616,10 @@ class StereoMatching {
                   "sm_refine_ext_config");
             pkr_on_ = Do_calPKR;
             se_on_ = Do_subpixelEnhancement;
+        }
+        if (Do_refine && Do_discontinuityAdjust) {
+            check(sm_refine_da_config(ctx_, 1, da_canny_low, da_canny_high, da_blur_side, da_blur_centre), "sm_refine_da_config");
+            da_on_ = true;
         }
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }

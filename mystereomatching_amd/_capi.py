@@ -26,6 +26,8 @@ CBCA_DW_DEFAULTS = (23, 23, 30, 0, 5.0)   # arm_l2, arm_l_out2, arm_c_thresh2, a
 SE_REFERENCE, SE_FLOAT = 0, 1
 # sm_refine_ext_config's values when a stage is on: pkr_ratio, disp_pkr, bg_ipl_depth, se_mode
 REFINE_EXT_DEFAULTS = (0.1, -64, 1000, SE_REFERENCE)
+# sm_refine_da_config's values: canny_low, canny_high, blur_side, blur_centre
+REFINE_DA_DEFAULTS = (20, 60, 84, 87)
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -121,6 +123,10 @@ SIGNATURES = [
     ("sm_get_pkr_mask", C.c_int, [_P, _P]),
     ("sm_get_subpixel", C.c_int, [_P, _P]),
     ("sm_download_subpixel", C.c_int, [_P, C.c_int32, _P]),
+    ("sm_refine_da_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("sm_get_da_edges", C.c_int, [_P, _P]),
+    ("sm_da_run_image", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
+    ("sm_set_da_edges", C.c_int, [_P, _P]),
 ]
 
 _lib = None

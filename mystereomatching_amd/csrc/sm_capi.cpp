@@ -482,7 +482,7 @@ sm_status sm_refine(sm_ctx* c, int16_t* disp_out) {
     if (!c->p.do_refine) return fail(c, SM_ESTATE, "sm_refine needs do_refine = 1 at sm_create (DP[1] is not computed otherwise)");
     if (c->stage != 4) return fail(c, SM_ESTATE, "sm_refine must follow sm_disp_optimize");
     if (refine_reads_volume(c) && c->p.optimization == SM_OPT_SGM && !c->p.keep_final_volume && !c->vt_on && !c->rx_vol_ok)
-        return fail(c, SM_ESTATE, "sm_refine: do_pkr / do_subpixel were switched on after sm_disp_optimize (SGM kept no path sum)");
+        return fail(c, SM_ESTATE, "sm_refine: do_pkr / do_subpixel / the discontinuity adjustment were switched on after sm_disp_optimize (SGM kept no path sum)");
     if ((s = wait_copy(c))) return s;
     if ((s = run_refine(c, at(c, 0, c->n_loaded, c->st)))) return s;
     c->stage = 5;
@@ -914,6 +914,93 @@ sm_status sm_download_subpixel(sm_ctx* c, int32_t n, float* dst) {
 }
 
 sm_status sm_get_subpixel(sm_ctx* c, float* dst) { return sm_download_subpixel(c, 1, dst); }
+
+// the discontinuity adjustment's scratch, on the first call that needs it (batch_capacity pairs)
+static sm_status da_alloc(sm_ctx* c) {
+    const size_t cap = (size_t)c->cap;
+    sm_status s;
+    if (!c->da_u8 && (s = dalloc(c, &c->da_u8, cap * sm::DA_PLANES * c->npix))) return s;
+    if (!c->da_mag && (s = dalloc(c, &c->da_mag, cap * c->npix))) return s;
+    if (!c->da_lab && (s = dalloc(c, &c->da_lab, cap * c->npix))) return s;
+    if (!c->da_hist && (s = dalloc(c, &c->da_hist, cap * 256))) return s;
+    return SM_OK;
+}
+
+sm_status sm_refine_da_config(sm_ctx* c, int32_t on, int32_t canny_low, int32_t canny_high, int32_t blur_side,
+                              int32_t blur_centre) {
+    if (!c) return SM_EINVAL;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (!c->p.do_refine) return fail(c, SM_EINVAL, "sm_refine_da_config: the context has do_refine = 0 (refine() never runs)");
+    if (c->p.optimization == SM_OPT_SO)
+        return fail(c, SM_EINVAL, "sm_refine_da_config: not with optimization so (the reference's so rewrites vm[0] in place)");
+    if (canny_low < 0 || canny_low > 32767) return fail(c, SM_EINVAL, "canny_low must be in [0, 32767]");
+    if (canny_high < 0 || canny_high > 32767) return fail(c, SM_EINVAL, "canny_high must be in [0, 32767]");
+    if (blur_side < 0) return fail(c, SM_EINVAL, "blur_side must be >= 0");
+    if (blur_centre < 0) return fail(c, SM_EINVAL, "blur_centre must be >= 0");
+    if (2 * (int64_t)blur_side + blur_centre > 256)
+        return fail(c, SM_EINVAL, "blur_side, blur_centre: 2 * side + centre must be <= 256 (8.8 fixed point)");
+    const bool live = c->st != nullptr;
+    if (live && on) {
+        if (!sm::refine_ext_shape_ok(c->p.rows, c->p.cols, c->cap))
+            return fail(c, SM_EINVAL, "sm_refine_da_config: rows * cols * batch_capacity too large");
+        sm_status s = check(c);
+        if (s) return s;
+        if ((s = da_alloc(c))) return s;
+        // SGM keeps its path sum in vm[0] only while a stage reads it (see sm_refine_ext_config)
+        if (!refine_reads_volume(c)) c->rx_vol_ok = false;
+    }
+    c->da_on = live && on;
+    c->da_low = canny_low;
+    c->da_high = canny_high;
+    c->da_ks = blur_side;
+    c->da_kc = blur_centre;
+    c->da_ran = false;
+    return SM_OK;
+}
+
+sm_status sm_get_da_edges(sm_ctx* c, uint8_t* dst) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!dst) return fail(c, SM_EINVAL, "null dst");
+    if (!c->da_on || !c->da_ran || c->stage < 5)
+        return fail(c, SM_ESTATE, "no edge map yet (sm_refine_da_config, then sm_refine / sm_run)");
+    return download_sync(c, dst, c->da_u8 + (size_t)sm::DA_EDGE * c->npix, c->npix);
+}
+
+sm_status sm_da_run_image(sm_ctx* c, const uint8_t* src, int32_t first_stage, uint8_t* out_eq, uint8_t* out_blur,
+                          uint8_t* out_edges) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!src) return fail(c, SM_EINVAL, "null src");
+    if (first_stage < 0 || first_stage > 2) return fail(c, SM_EINVAL, "first_stage must be 0 (equalise), 1 (blur) or 2 (Canny)");
+    if (!sm::refine_ext_shape_ok(c->p.rows, c->p.cols, c->cap)) return fail(c, SM_EINVAL, "rows * cols * batch_capacity too large");
+    if ((s = da_alloc(c))) return s;
+    c->da_ran = false;   // pair 0's planes are this call's from here on
+    uint8_t* planes = c->da_u8;
+    HIP_TRY(c, hipMemcpyAsync(planes + (size_t)(first_stage == 2 ? sm::DA_BLUR : sm::DA_EQ) * c->npix, src, c->npix,
+                              hipMemcpyHostToDevice, c->st));
+    if ((s = run_da_image(c, at(c, 0, 1, c->st), first_stage, nullptr))) return s;
+    if (out_eq && first_stage == 0) HIP_TRY(c, hipMemcpyAsync(out_eq, planes + (size_t)sm::DA_EQ * c->npix, c->npix, hipMemcpyDeviceToHost, c->st));
+    if (out_blur && first_stage <= 1)
+        HIP_TRY(c, hipMemcpyAsync(out_blur, planes + (size_t)sm::DA_BLUR * c->npix, c->npix, hipMemcpyDeviceToHost, c->st));
+    if (out_edges) HIP_TRY(c, hipMemcpyAsync(out_edges, planes + (size_t)sm::DA_EDGE * c->npix, c->npix, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    return SM_OK;
+}
+
+sm_status sm_set_da_edges(sm_ctx* c, const uint8_t* edges) {
+    sm_status s = check(c);
+    if (s) return s;
+    if (!edges) {
+        c->da_user_on = false;
+        return SM_OK;
+    }
+    if (!c->da_user && (s = dalloc(c, &c->da_user, c->npix))) return s;
+    HIP_TRY(c, hipMemcpyAsync(c->da_user, edges, c->npix, hipMemcpyHostToDevice, c->st));
+    HIP_TRY(c, hipStreamSynchronize(c->st));
+    c->da_user_on = true;
+    return SM_OK;
+}
 
 void sm_bgr2lab_host(const uint8_t* bgr, size_t npix, uint8_t* lab) {
     if (!bgr || !lab) return;

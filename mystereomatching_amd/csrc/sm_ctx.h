@@ -129,6 +129,17 @@ struct sm_ctx {
     float* se_tmp = nullptr;       // [cap][npix] SE before it (the median filters a copy)
     bool rx_pkr_ran = false, rx_se_ran = false;   // the last refine filled the mask / the float maps
     bool rx_vol_ok = true;         // no volume-reading stage was switched on since dispOptimize last ran
+    // refine()'s Do_discontinuityAdjust stage (sm_refine_da_config; sm_refine_da.hip)
+    bool da_on = false;
+    int da_low = 20, da_high = 60; // Canny's thresholds (cpp:6064)
+    int da_ks = 84, da_kc = 87;    // GaussianBlur(3 x 3, sigma 4) in 8.8 fixed point
+    uint8_t* da_u8 = nullptr;      // [cap][DA_PLANES][npix]
+    uint16_t* da_mag = nullptr;    // [cap][npix]
+    int* da_lab = nullptr;         // [cap][npix]
+    int* da_hist = nullptr;        // [cap][256]
+    uint8_t* da_user = nullptr;    // [npix] sm_set_da_edges' map
+    bool da_user_on = false;       // the next refine takes da_user for every pair instead of Canny's map
+    bool da_ran = false;           // pair 0's DA_EDGE plane holds the last refine's edge map
     // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -418,6 +429,7 @@ sm_status run_cbca(sm_ctx* c, int view, bool fuse_scale, float w, const Group& G
 sm_status run_scale(sm_ctx* c, int view, float w, const Group& G);
 sm_status run_optimize(sm_ctx* c, int view, const Group& G);
 sm_status run_refine(sm_ctx* c, const Group& G);
+sm_status run_da_image(sm_ctx* c, const Group& G, int first, const int16_t* dp);
 
 // sm_stages_agg.cpp
 sm_status nl_open(sm_ctx* c, hipStream_t st);

@@ -398,4 +398,32 @@ void launch_subpixel(const int16_t* dp, const float* vm, float* se, int n, int H
                      hipStream_t st);
 void launch_median3_f32(const float* src, float* dst, int n, int H, int W, hipStream_t st);
 
+// refine()'s Do_discontinuityAdjust stage (sm_refine_da.hip); pair-relative bases.  The u8 scratch of a pair:
+enum { DA_EQ = 0,      // DP[0] as 8 bits, equalised in place
+       DA_BLUR = 1,    // after the Gaussian
+       DA_EDGE = 2,    // Canny's edge map (0 / 255), or the one sm_set_da_edges supplied
+       DA_CAND = 3,    // 0, 1 (candidate), 2 (candidate above the high threshold)
+       DA_DIR = 4,     // the ordered pass's direction per pixel, 0xff where it changes nothing
+       DA_FLAG = 5,    // 1 on the union-find root of a component that holds a strong candidate
+       DA_PLANES = 6 };
+struct DaArgs {
+    uint8_t* u8;                // [n][DA_PLANES][H][W]
+    uint16_t* mag;              // [n][H][W] |dx| + |dy| (12 bits) | NMS sector << 12
+    int* lab;                   // [n][H][W] union-find parents, pair-local pixel indices (-1: no candidate)
+    int* hist;                  // [n][256], zeroed before launch_da_hist
+    int H, W, n;
+    int low, high;              // Canny's thresholds, low <= high
+    int ks, kc;                 // the Gaussian's side and centre taps (8.8 fixed point)
+};
+void launch_da_hist(const DaArgs& a, const int16_t* dp, hipStream_t st);   // dp null: the image already in DA_EQ
+void launch_da_equalize(const DaArgs& a, hipStream_t st);
+void launch_da_blur(const DaArgs& a, hipStream_t st);
+void launch_da_sobel(const DaArgs& a, hipStream_t st);
+void launch_da_nms(const DaArgs& a, hipStream_t st);
+void launch_da_link(const DaArgs& a, hipStream_t st);
+void launch_da_mark(const DaArgs& a, hipStream_t st);
+void launch_da_edges(const DaArgs& a, hipStream_t st);
+void launch_da_dir(const DaArgs& a, const int16_t* src, int16_t* dst, hipStream_t st);   // dst = src
+void launch_da_adjust(const DaArgs& a, const int16_t* src, int16_t* dst, const float* vm, int D, hipStream_t st);
+
 }  // namespace sm

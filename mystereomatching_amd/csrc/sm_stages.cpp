@@ -460,6 +460,42 @@ sm_status run_optimize(sm_ctx* c, int view, const Group& G) {
     return SM_OK;
 }
 
+static sm::DaArgs da_args(sm_ctx* c, const Group& G) {
+    sm::DaArgs a{};
+    a.u8 = G.slice(c->da_u8, (size_t)sm::DA_PLANES * c->npix);
+    a.mag = G.slice(c->da_mag, c->npix);
+    a.lab = G.slice(c->da_lab, c->npix);
+    a.hist = G.slice(c->da_hist, 256);
+    a.H = c->p.rows;
+    a.W = c->p.cols;
+    a.n = G.n;
+    a.low = std::min(c->da_low, c->da_high);   // Canny swaps thresholds given in the wrong order
+    a.high = std::max(c->da_low, c->da_high);
+    a.ks = c->da_ks;
+    a.kc = c->da_kc;
+    return a;
+}
+
+// discontinuityAdjust's image stages (cpp:6059-6064) for the group's pairs, entered at `first`: 0 equalizeHist (on
+// `dp` as 8 bits, or with dp null on the image already in the DA_EQ plane), 1 GaussianBlur (on DA_EQ), 2 Canny (on
+// DA_BLUR); the edge map ends in the DA_EDGE plane.  A fixed sequence of launches, nothing read back.
+sm_status run_da_image(sm_ctx* c, const Group& G, int first, const int16_t* dp) {
+    const sm::DaArgs a = da_args(c, G);
+    const double np = (double)G.n * c->npix;
+    sm_status s;
+    if (first <= 0) {
+        HIP_TRY(c, hipMemsetAsync(a.hist, 0, (size_t)G.n * 256 * sizeof(int), G.st));
+        if ((s = timed(c, G.st, "refine_da_hist", np * (dp ? 3 : 1), [&] { sm::launch_da_hist(a, dp, G.st); }))) return s;
+        if ((s = timed(c, G.st, "refine_da_equalize", np * 2, [&] { sm::launch_da_equalize(a, G.st); }))) return s;
+    }
+    if (first <= 1 && (s = timed(c, G.st, "refine_da_blur", np * 2, [&] { sm::launch_da_blur(a, G.st); }))) return s;
+    if ((s = timed(c, G.st, "refine_da_sobel", np * 3, [&] { sm::launch_da_sobel(a, G.st); }))) return s;
+    if ((s = timed(c, G.st, "refine_da_nms", np * (2 + 1 + 1 + 4), [&] { sm::launch_da_nms(a, G.st); }))) return s;
+    if ((s = timed(c, G.st, "refine_da_link", np * (1 + 4), [&] { sm::launch_da_link(a, G.st); }))) return s;
+    if ((s = timed(c, G.st, "refine_da_mark", np * 1, [&] { sm::launch_da_mark(a, G.st); }))) return s;
+    return timed(c, G.st, "refine_da_edges", np * (1 + 4 + 1), [&] { sm::launch_da_edges(a, G.st); });
+}
+
 // refine(), non-USE_RECONCV branch (cpp:1347-1510), on DP[0] of n pairs: LR check (in place),
 // region votes and proper interpolations (Jacobi, ping-pong with disp_tmp), 3x3 median.
 sm_status run_refine(sm_ctx* c, const Group& G) {
@@ -512,6 +548,24 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
         // k_bg_r reads the map and writes r; k_bg_scan reads both and writes the map
         if ((s = timed(c, G.st, "refine_bg_ipol", 4 * map, [&] { sm::launch_bg_ipol(a, G.st); }))) return s;
         std::swap(cur, nxt);
+    }
+    if (c->da_on) {   // discontinuityAdjust(DP[0]) (cpp:1473-1476) on vm[0] as dispOptimize left it
+        const sm::DaArgs a = da_args(c, G);
+        if (c->da_user_on) {   // sm_set_da_edges: the supplied map for every pair
+            for (int i = 0; i < G.n; i++)
+                HIP_TRY(c, hipMemcpyAsync(a.u8 + ((size_t)i * sm::DA_PLANES + sm::DA_EDGE) * c->npix, c->da_user, c->npix,
+                                          hipMemcpyDeviceToDevice, G.st));
+        } else if ((s = run_da_image(c, G, 0, cur))) {
+            return s;
+        }
+        // k_da_dir reads the map and the edge map's 3 x 3, writes the copy and the directions; k_da_adjust touches
+        // the directions and, per pixel it can change, three map values and three costs
+        if ((s = timed(c, G.st, "refine_da_dir", np * (2 + 1 + 2 + 1), [&] { sm::launch_da_dir(a, cur, nxt, G.st); }))) return s;
+        if ((s = timed(c, G.st, "refine_da_adjust", np * 1,
+                       [&] { sm::launch_da_adjust(a, cur, nxt, G.vm0, p.num_disparities, G.st); })))
+            return s;
+        std::swap(cur, nxt);
+        c->da_ran = true;
     }
     if (c->rx_se) {   // subpixelEnhancement + medianBlur(SE, SE, 3) (cpp:1482-1495); DP[0] stays
         float* raw = G.slice(c->se_tmp, c->npix);

@@ -67,7 +67,7 @@ int cbca_lag2(const sm_ctx* c) { return c->dw_l_out > c->p.arm_min_l ? c->dw_l_o
 // reads cbca_iterations
 int cbca_iters(const sm_ctx* c) { return c->dw_on ? 2 : c->p.cbca_iterations; }
 // refine()'s calPKR / subpixelEnhancement are on: they read vm[0] after dispOptimize
-bool refine_reads_volume(const sm_ctx* c) { return c->p.do_refine && (c->rx_pkr || c->rx_se); }
+bool refine_reads_volume(const sm_ctx* c) { return c->p.do_refine && (c->rx_pkr || c->rx_se || c->da_on); }
 
 // combine2Vm_4's predicate on the nine-term sum s of integer arm maxima is boxFilter's (float)(s * (1.0 / 9))
 // (double sums, one rounding) < thres.  The product and its rounding are non-decreasing in s, so for every

@@ -61,6 +61,12 @@ class StereoMatching:
     Do_subpixelEnhancement = False
     SE_FLOAT = False
     PKR_RATIO = _capi.REFINE_EXT_DEFAULTS[0]   # calPKR's local ratio_PKR (cpp:4093)
+    # refine()'s discontinuity adjustment (h:78; sm_refine_da_config), off in the shipped build: equalizeHist,
+    # GaussianBlur and Canny on DP[0] as 8 bits, then the raster-order pass of cpp:6069-6135; refine() leaves the
+    # edge map in self.DA_Edge.  DA_CANNY / DA_BLUR_TAPS are the literals of cpp:6063-6064 in the restated form
+    Do_discontinuityAdjust = False
+    DA_CANNY = _capi.REFINE_DA_DEFAULTS[:2]
+    DA_BLUR_TAPS = _capi.REFINE_DA_DEFAULTS[2:]
 
     class Parameters:
         """StereoMatching::Parameters (h:85-351): the fields the hot path reads."""
@@ -217,6 +223,12 @@ class StereoMatching:
                                                 int(self.Do_bgIpol), int(param.bgIplDepth), int(self.Do_subpixelEnhancement),
                                                 _capi.SE_FLOAT if self.SE_FLOAT else _capi.SE_REFERENCE)
             _capi.check(self._lib, ctx, st, "sm_refine_ext_config")
+        self.DA_Edge: Optional[np.ndarray] = None       # discontinuityAdjust's edge map (Do_discontinuityAdjust)
+        self._refine_da = self._refine_on and bool(self.Do_discontinuityAdjust)
+        if self._refine_da:
+            st = self._lib.sm_refine_da_config(ctx, 1, int(self.DA_CANNY[0]), int(self.DA_CANNY[1]),
+                                               int(self.DA_BLUR_TAPS[0]), int(self.DA_BLUR_TAPS[1]))
+            _capi.check(self._lib, ctx, st, "sm_refine_da_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -246,7 +258,7 @@ class StereoMatching:
 
     def refine(self):
         """refine() (cpp:1138-1511): LR check against DP[1], [peak-ratio check,] region votes, proper
-        interpolation, [background fill, sub-pixel map -> SE,] 3x3 median -> DP[0].  Needs Do_refine = True when
+        interpolation, [background fill, discontinuity adjustment -> DA_Edge, sub-pixel map -> SE,] 3x3 median -> DP[0].  Needs Do_refine = True when
         the object was constructed."""
         dp = np.empty((self.h_, self.w_), np.int16)
         _capi.check(self._lib, self._ctx, self._lib.sm_refine(self._ctx, _capi.ptr(dp)), "refine")
@@ -257,6 +269,9 @@ class StereoMatching:
         if self._refine_ext[2]:
             self.SE = np.empty((self.h_, self.w_), np.float32)
             _capi.check(self._lib, self._ctx, self._lib.sm_get_subpixel(self._ctx, _capi.ptr(self.SE)), "SE")
+        if self._refine_da:
+            self.DA_Edge = np.empty((self.h_, self.w_), np.uint8)
+            _capi.check(self._lib, self._ctx, self._lib.sm_get_da_edges(self._ctx, _capi.ptr(self.DA_Edge)), "DA_Edge")
         return dp
 
     def pipeline(self):
@@ -364,6 +379,8 @@ class StereoBatch:
         intersect = bool(overrides.pop("cbca_intersect", True))
         # refine()'s extra stages (sm_refine_ext_config): refine_ext is a dict of refine_ext_config's arguments
         refine_ext = overrides.pop("refine_ext", None)
+        # refine()'s discontinuity adjustment (sm_refine_da_config): refine_da is a dict of refine_da_config's arguments
+        refine_da = overrides.pop("refine_da", None)
         p = _capi.default_params(max_disp, rows, cols, **overrides)
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
@@ -383,6 +400,8 @@ class StereoBatch:
             self.cbca_intersect_config(False)
         if refine_ext:
             self.refine_ext_config(**dict(refine_ext))
+        if refine_da:
+            self.refine_da_config(**dict(refine_da))
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -546,6 +565,21 @@ class StereoBatch:
         st = self._lib.sm_refine_ext_config(self._ctx, int(bool(do_pkr)), float(pkr_ratio), int(disp_pkr),
                                             int(bool(do_bg_ipol)), int(bg_ipl_depth), int(bool(do_subpixel)), int(se_mode))
         _capi.check(self._lib, self._ctx, st, "refine_ext_config")
+
+    def refine_da_config(self, on: bool = True, canny_low: int = _capi.REFINE_DA_DEFAULTS[0],
+                         canny_high: int = _capi.REFINE_DA_DEFAULTS[1], blur_side: int = _capi.REFINE_DA_DEFAULTS[2],
+                         blur_centre: int = _capi.REFINE_DA_DEFAULTS[3]):
+        """sm_refine_da_config: refine()'s discontinuity adjustment (off by default), from the next run on; needs
+        do_refine = 1 and an optimization other than "so"."""
+        st = self._lib.sm_refine_da_config(self._ctx, int(bool(on)), int(canny_low), int(canny_high), int(blur_side),
+                                           int(blur_centre))
+        _capi.check(self._lib, self._ctx, st, "refine_da_config")
+
+    def get_da_edges(self) -> np.ndarray:
+        """sm_get_da_edges: the first pair's edge map [H][W] (0 / 255) of the last run with the adjustment on."""
+        out = np.empty(self.shape[:2], np.uint8)
+        _capi.check(self._lib, self._ctx, self._lib.sm_get_da_edges(self._ctx, _capi.ptr(out)), "get_da_edges")
+        return out
 
     def get_pkr_mask(self) -> np.ndarray:
         """sm_get_pkr_mask: the first pair's PKR_Err_Mask [H][W] of the last run with do_pkr on."""

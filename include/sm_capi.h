@@ -49,6 +49,7 @@
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
  *   sm_run / sm_run_batch  <- the whole main_.cpp:139-163 sequence for n independent pairs
  *   sm_run_batch_multi     <- the same over several contexts / GPUs (one host thread each)
+ *   sm_pyramid_config      <- PY_LEV and the per-level constructor arguments of main_.cpp:131-158, for sm_run
  * Threading: one sm_ctx per host thread; each ctx owns one HIP stream on its device.
  */
 #ifndef SM_CAPI_H
@@ -280,10 +281,41 @@ SM_API sm_status sm_get_arms(sm_ctx* ctx, int32_t view, uint16_t* dst);  /* H*W*
  * device-to-device).  A device source must be complete before the call (its stream synchronized). */
 SM_API sm_status sm_upload_batch(sm_ctx* ctx, int32_t n, const uint8_t* lbgr, const uint8_t* rbgr,
                                  const uint8_t* lgray, const uint8_t* rgray);
-/* Run cost -> CBCA -> SolveAll(py_lev=1, reg_lambda) -> SGM -> WTA [-> refine] on the n uploaded pairs.
+/* Run cost -> CBCA -> SolveAll(PY_LVL, reg_lambda) -> SGM -> WTA [-> refine] on the n uploaded pairs; PY_LVL is
+ * 1 unless sm_pyramid_config set another (then every pair group first builds and aggregates its coarse levels).
  * Asynchronous on the ctx stream.  disp_out: host or device [n][H][W] int16 (synchronous copy) or
  * NULL to leave the maps on the device (read them with sm_download_disp). */
 SM_API sm_status sm_run(sm_ctx* ctx, int32_t n, float reg_lambda, int16_t* disp_out);
+/* The cross-scale pyramid of main_.cpp:131-158 inside sm_run / sm_run_batch / sm_run_batch_multi: py_lvl = PY_LEV in
+ * [1, 8]; 1 (the default) is sm_run without a pyramid.  With py_lvl = L > 1 the context owns L - 1 level contexts --
+ * ordinary contexts on the same device with the same batch_capacity, created as sm_create creates one, destroyed by
+ * sm_destroy or the next sm_pyramid_config.  Level s >= 1 takes level 0's sm_params except (main_.cpp:138-148,
+ * cpp:5367-5371): rows_s = (rows_{s-1} + 1) / 2 and cols_s likewise; num_disparities_s = (num_disparities_{s-1} - 1)
+ * / 2 + 2; arm_l_s = arm_l / 2^s and arm_l_out_s = arm_l_out / 2^s; optimization "" (no optimiser or refine buffers;
+ * do_refine still decides that vm[1] is built and combined), one stream, no placement trials.  fuse_cost_scan and
+ * fuse_norm_scan are decided per level from its own size.  Memory: 1/8 + 1/64 + .. of level 0's volumes and planes.
+ * sm_run then does, for every pair group on the group's stream: pyrDown of the group's colour and gray images of
+ * both views, level by level (one launch per level); prep, cost volume(s) and aggregation of levels L - 1 .. 1;
+ * level 0 with SolveAll not fused into its last aggregation store; SolveAll's cross-scale sum (cpp:2179-2203: from
+ * 0.f, one rounded product and one rounded sum per level in level order, cy >>= 1, cx >>= 1, cd = (cd + 1) >> 1)
+ * into level 0's vm[0] (and vm[1] with do_refine); level 0's optimiser and refine().  The maps are the same for every
+ * schedule; the NL pipelined front is off.  Profile names of a level's launches end in @<level>
+ * ("cbca_v_norm_scan@1"); the new launches are "pyr_down@<destination level>" and "solve_all_pyr[_r]".
+ * sm_aws_config, sm_bf_config, sm_gfnl_config, sm_cbca_double_config (arm_l2 and arm_l_out2 divided by 2^s) and
+ * sm_cbca_intersect_config apply to every level, whichever order they and this call come in; a level that cannot
+ * take a setting fails that call with the level named and every level unchanged.  sm_vmtop_config,
+ * sm_refine_ext_config and sm_refine_da_config concern level 0 only.  The staged calls keep their contracts
+ * (sm_solve_all refuses py_lev != 1; sm_solve_all_pyr takes one context per level).
+ * Checked before any device call: py_lvl outside [1, 8] and a level that sm_create would refuse (rows or cols < 2,
+ * an aggregation's minimum size, ..) are SM_EINVAL with the level and its reason in sm_last_error.  On a live
+ * context the call joins a live pipeline and waits for the queued work first.  If a level cannot be allocated the
+ * context is left at py_lvl = 1. */
+SM_API sm_status sm_pyramid_config(sm_ctx* ctx, int32_t py_lvl);
+/* Level `level`'s context, borrowed: level 0 is ctx itself; NULL when out of range.  For sm_get_volume, sm_get_arms,
+ * sm_get_census, sm_get_cbca_area and sm_get_cbca_dw_mask on a coarse level after sm_run -- call
+ * sm_synchronize(ctx) on the owner first.  Every other call on a level context returns SM_ESTATE. */
+SM_API sm_ctx* sm_pyramid_level(sm_ctx* ctx, int32_t level);
+SM_API int32_t sm_pyramid_levels(const sm_ctx* ctx);   /* PY_LVL of the context (1 without a pyramid) */
 SM_API sm_status sm_download_disp(sm_ctx* ctx, int32_t n, int16_t* disp_out);
 /* The same copy, enqueued on the ctx's copy stream behind the work queued so far, returning at
  * once: the next sm_run's disparity-writing kernels wait for it, so the copy overlaps the next

@@ -85,6 +85,9 @@ SIGNATURES = [
     ("sm_get_arms", C.c_int, [_P, C.c_int32, _P]),
     ("sm_upload_batch", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("sm_run", C.c_int, [_P, C.c_int32, C.c_float, _P]),
+    ("sm_pyramid_config", C.c_int, [_P, C.c_int32]),
+    ("sm_pyramid_level", C.c_void_p, [_P, C.c_int32]),
+    ("sm_pyramid_levels", C.c_int32, [_P]),
     ("sm_download_disp", C.c_int, [_P, C.c_int32, _P]),
     ("sm_download_disp_async", C.c_int, [_P, C.c_int32, _P]),
     ("sm_upload_batch_async", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),

@@ -1,7 +1,8 @@
 // sm_capi.cpp — C-ABI of libsm_hip.so: the context's life (sm_create, sm_destroy and the buffers they own),
 // the entry points in the reference's StereoMatching call order (see include/sm_capi.h for the file:line of
 // each reference interface), the pyramid weights, getters and setters (sm_download_subpixel among them, beside
-// the stage it reads), the features' *_config calls, profiling, sm_cal_err and the diagnostics.  The batch
+// the stage it reads), the features' *_config calls (the aggregation-side ones over every pyramid level), the batch
+// path's pyramid (sm_pyramid_config and the level contexts it owns), profiling, sm_cal_err and the diagnostics.  The batch
 // path is sm_run.cpp, the stage drivers sm_stages.cpp and sm_stages_agg.cpp, parameter checks sm_validate.cpp.
 // No exceptions cross the ABI.
 #include <math.h>
@@ -73,6 +74,7 @@ sm_status download_sync(sm_ctx* c, void* dst, const void* src, size_t bytes) {
 }
 
 void free_all(sm_ctx* c) {
+    if (c->owner) c->nl_st = nullptr;   // (a level context's NL front stream is its owner's)
     for (void* q : c->allocs) hipFree(q);
     c->allocs.clear();
     // every stream is drained and destroyed (the main stream last) before the events its work recorded or waited for
@@ -99,14 +101,16 @@ void free_all(sm_ctx* c) {
 
 }  // namespace
 
-extern "C" {
-
-sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
+// sm_create; with `owner`, pyramid level `level` of that context (sm_pyramid_config), which needs no map or
+// refine planes beyond DP[0]'s
+static sm_status create_ctx(sm_ctx** out, const sm_params* p, int32_t hip_device, sm_ctx* owner, int level) {
     if (!out || !p) return SM_EINVAL;
     *out = nullptr;
     sm_ctx* c = new (std::nothrow) sm_ctx();
     if (!c) return SM_ENOMEM;
     *out = c;  // returned even on failure so sm_last_error works; caller must sm_destroy
+    c->owner = owner;
+    c->level = level;
     // a struct from another version of sm_capi.h (or not filled by sm_params_default) is refused
     // before any field past struct_size is read
     if (p->struct_size != (uint32_t)sizeof(sm_params))
@@ -160,9 +164,9 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
         if ((s = dalloc(c, &c->so_trace, cap * c->nvol))) return s;
         if ((s = dalloc(c, &c->so_cidx, cap * c->npix))) return s;
     }
-    if (p->do_refine || p->optimization == SM_OPT_SO)
+    if ((p->do_refine && !owner) || p->optimization == SM_OPT_SO)
         if ((s = dalloc(c, &c->disp1, cap * c->npix))) return s;
-    if (p->do_refine) {
+    if (p->do_refine && !owner) {
         if ((s = dalloc(c, &c->flags1, cap * c->npix))) return s;
         if ((s = dalloc(c, &c->disp_tmp, cap * c->npix))) return s;
     }
@@ -262,11 +266,31 @@ sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) {
     return SM_OK;
 }
 
+// every stream of the context idle (its levels' work runs on them too)
+static void drain(sm_ctx* c) {
+    for (hipStream_t st : {c->nl_st, c->cst, c->xst[0], c->xst[1], c->xst[2], c->st})
+        if (st) hipStreamSynchronize(st);
+}
+
+static void destroy_levels(sm_ctx* c) {
+    for (sm_ctx* q : c->levels) {
+        free_all(q);
+        delete q;
+    }
+    c->levels.clear();
+}
+
+extern "C" {
+
+sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) { return create_ctx(out, p, hip_device, nullptr, 0); }
+
 sm_status sm_destroy(sm_ctx* c) {
     if (!c) return SM_OK;
+    if (c->owner) return refuse_level(c);   // (its owner destroys it)
     hipSetDevice(c->device);
     if (c->pipe_live) join_all(c);
-    if (c->st) hipStreamSynchronize(c->st);
+    drain(c);
+    destroy_levels(c);
     free_all(c);
     delete c;
     return SM_OK;
@@ -347,7 +371,7 @@ static bool lu_inv_row0(int L, float (*M)[sm::kMaxPyr], float* w) {
     return true;
 }
 
-static bool pyr_weights(int L, float lam, float* w) {
+extern "C++" bool pyr_weights(int L, float lam, float* w) {
     float M[sm::kMaxPyr][sm::kMaxPyr] = {};
     for (int s = 0; s < L; s++) {
         if (s == 0) {
@@ -515,7 +539,7 @@ sm_status sm_set_disp(sm_ctx* c, int32_t view, const int16_t* src) {
 }
 
 sm_status sm_get_volume(sm_ctx* c, int32_t view, float* dst) {
-    sm_status s = check(c);
+    sm_status s = check_any(c);
     if (s) return s;
     if (!dst) return fail(c, SM_EINVAL, "null dst");
     if (c->stage < 2) return fail(c, SM_ESTATE, "no volume yet");
@@ -563,7 +587,7 @@ sm_status sm_get_top_disp(sm_ctx* c, int32_t view, float* dst) {
 }
 
 sm_status sm_get_arms(sm_ctx* c, int32_t view, uint16_t* dst) {
-    sm_status s = check(c);
+    sm_status s = check_any(c);
     if (s) return s;
     if (!dst || view < 0 || view > 1) return fail(c, SM_EINVAL, "bad arguments");
     if (c->stage < 2 || !needs_arms(c->p)) return fail(c, SM_ESTATE, "arms not computed");
@@ -579,7 +603,7 @@ sm_status sm_get_arms(sm_ctx* c, int32_t view, uint16_t* dst) {
 }
 
 sm_status sm_get_census(sm_ctx* c, int32_t view, uint64_t* dst) {
-    sm_status s = check(c);
+    sm_status s = check_any(c);
     if (s) return s;
     if (!dst || view < 0 || view > 1) return fail(c, SM_EINVAL, "bad arguments");
     if (c->stage < 2 || !needs_census(c->p)) return fail(c, SM_ESTATE, "census not computed");
@@ -603,7 +627,7 @@ void* sm_stream(sm_ctx* c) {
 }
 
 sm_status sm_profile_enable(sm_ctx* c, int32_t on) {
-    if (!c) return SM_EINVAL;
+    if (sm_status r = refuse_level(c)) return r;
     c->prof = on != 0;
     return SM_OK;
 }
@@ -680,23 +704,53 @@ sm_status sm_cal_err(const int16_t* DP, const float* DT, const uint8_t* mask, in
 
 float sm_expf_host(float x) { return sm::expf_host(x); }
 
-sm_status sm_aws_config(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gamma_c) {
+// The aggregation-side *_config calls apply to every pyramid level: `one(context, level, dry)` is the call's
+// per-context half; a dry pass over all levels checks the arguments (host code only) before the second pass
+// changes anything, so a level that cannot take the setting fails the call, named, with every level unchanged.
+extern "C++" {
+template <typename F>
+static sm_status on_levels(sm_ctx* c, F&& one) {
+    sm_status s = refuse_level(c);
+    if (s) return s;
+    const int L = 1 + (int)c->levels.size();
+    for (int dry = 1; dry >= 0; dry--) {
+        if (!dry && L > 1) {   // the levels' buffers are used by work on the owner's streams
+            if ((s = check(c))) return s;
+            HIP_TRY(c, hipStreamSynchronize(c->st));
+        }
+        for (int l = 0; l < L; l++) {
+            sm_ctx* q = l ? c->levels[l - 1] : c;
+            if ((s = one(q, l, dry != 0))) {
+                if (l) c->err = "pyramid level " + std::to_string(l) + ": " + q->err;
+                return s;
+            }
+        }
+    }
+    return SM_OK;
+}
+}  // extern "C++"
+
+static sm_status aws_config_one(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gamma_c, bool dry) {
     // host state only (launches already queued carry their constants by value): no device call,
     // so the arguments are checked on a machine without a GPU too
-    if (!c) return SM_EINVAL;
     if (c->p.aggregation != SM_AGG_AWS) return fail(c, SM_EINVAL, "sm_aws_config: the context's aggregation is not SM_AGG_AWS");
     if (radius_v < 0 || radius_v > sm::AWS_MAX_R) return fail(c, SM_EINVAL, "radius_v must be in [0, 17]");
     if (radius_u < 0 || radius_u > sm::AWS_MAX_R) return fail(c, SM_EINVAL, "radius_u must be in [0, 17]");
     if (!(gamma_c > 0) || !std::isfinite(gamma_c)) return fail(c, SM_EINVAL, "gamma_c must be finite and > 0");
+    if (dry) return SM_OK;
     c->aws_rv = radius_v;
     c->aws_ru = radius_u;
     c->aws_gamma = gamma_c;
     return SM_OK;
 }
 
+sm_status sm_aws_config(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gamma_c) {
+    return on_levels(c, [&](sm_ctx* q, int, bool dry) { return aws_config_one(q, radius_v, radius_u, gamma_c, dry); });
+}
+
 sm_status sm_vmtop_config(sm_ctx* c, int32_t enable, int32_t method, int32_t num, float thres, int32_t ts, int32_t has_cir2,
                           int32_t cir3_color_limit) {
-    if (!c) return SM_EINVAL;
+    if (sm_status r = refuse_level(c)) return r;
     // the arguments are checked before any device call, so on a machine without a GPU too
     if (method < 0 || method > 2) return fail(c, SM_EINVAL, "method must be 0, 1 or 2 (vmTop_method)");
     if (num < 1 || num > sm::VMTOP_MAX_NUM) return fail(c, SM_EINVAL, "num must be in [1, 8] (vmTop_Num)");
@@ -732,25 +786,33 @@ sm_status sm_vmtop_config(sm_ctx* c, int32_t enable, int32_t method, int32_t num
     return SM_OK;
 }
 
-sm_status sm_bf_config(sm_ctx* c, int32_t ksize_v, int32_t ksize_u) {
+static sm_status bf_config_one(sm_ctx* c, int32_t ksize_v, int32_t ksize_u, bool dry) {
     // host state only, like sm_aws_config
-    if (!c) return SM_EINVAL;
     if (c->p.aggregation != SM_AGG_BF) return fail(c, SM_EINVAL, "sm_bf_config: the context's aggregation is not SM_AGG_BF");
     if (ksize_v < 1 || ksize_v > sm::BF_MAX_K) return fail(c, SM_EINVAL, "ksize_v must be in [1, 32]");
     if (ksize_u < 1 || ksize_u > sm::BF_MAX_K) return fail(c, SM_EINVAL, "ksize_u must be in [1, 32]");
     if (c->p.rows < ksize_v / 2 + 1) return fail(c, SM_EINVAL, "ksize_v: rows must be >= ksize_v / 2 + 1 (one reflection)");
     if (c->p.cols < ksize_u / 2 + 1) return fail(c, SM_EINVAL, "ksize_u: cols must be >= ksize_u / 2 + 1 (one reflection)");
+    if (dry) return SM_OK;
     c->bf_kv = ksize_v;
     c->bf_ku = ksize_u;
     return SM_OK;
 }
 
-sm_status sm_gfnl_config(sm_ctx* c, float var_thresh) {
-    if (!c) return SM_EINVAL;
+sm_status sm_bf_config(sm_ctx* c, int32_t ksize_v, int32_t ksize_u) {
+    return on_levels(c, [&](sm_ctx* q, int, bool dry) { return bf_config_one(q, ksize_v, ksize_u, dry); });
+}
+
+static sm_status gfnl_config_one(sm_ctx* c, float var_thresh, bool dry) {
     if (c->p.aggregation != SM_AGG_GFNL) return fail(c, SM_EINVAL, "sm_gfnl_config: the context's aggregation is not SM_AGG_GFNL");
     if (!std::isfinite(var_thresh)) return fail(c, SM_EINVAL, "var_thresh must be finite");
+    if (dry) return SM_OK;
     c->gfnl_thresh = var_thresh;
     return SM_OK;
+}
+
+sm_status sm_gfnl_config(sm_ctx* c, float var_thresh) {
+    return on_levels(c, [&](sm_ctx* q, int, bool dry) { return gfnl_config_one(q, var_thresh, dry); });
 }
 
 sm_status sm_get_gfnl_mask(sm_ctx* c, uint8_t* dst) {
@@ -762,9 +824,8 @@ sm_status sm_get_gfnl_mask(sm_ctx* c, uint8_t* dst) {
     return download_sync(c, dst, c->gfnl_mask, c->npix);
 }
 
-sm_status sm_cbca_double_config(sm_ctx* c, int32_t enable, int32_t arm_l2, int32_t arm_l_out2, int32_t arm_c_thresh2,
-                                int32_t arm_c_thresh_out2, float arm_len_thres) {
-    if (!c) return SM_EINVAL;
+static sm_status dw_config_one(sm_ctx* c, int32_t enable, int32_t arm_l2, int32_t arm_l_out2, int32_t arm_c_thresh2,
+                               int32_t arm_c_thresh_out2, float arm_len_thres, bool dry) {
     // the arguments are checked before any device call, so on a machine without a GPU too
     if (c->p.aggregation != SM_AGG_CBCA)
         return fail(c, SM_EINVAL, "sm_cbca_double_config: the context's aggregation is not SM_AGG_CBCA");
@@ -773,9 +834,10 @@ sm_status sm_cbca_double_config(sm_ctx* c, int32_t enable, int32_t arm_l2, int32
     if (arm_c_thresh2 < 0) return fail(c, SM_EINVAL, "arm_c_thresh2 must be >= 0 (cbca_cTresh[1])");
     if (arm_c_thresh_out2 < 0) return fail(c, SM_EINVAL, "arm_c_thresh_out2 must be >= 0 (cbca_cTresh_out[1])");
     if (!std::isfinite(arm_len_thres)) return fail(c, SM_EINVAL, "arm_len_thres must be finite (armLthres)");
+    if (dry) return SM_OK;
     const bool on = enable != 0 && c->st != nullptr;
     if (c->st) {   // a live context: nothing queued may still use the old settings' buffers
-        sm_status s = check(c);
+        sm_status s = check_any(c);
         if (s) return s;
         const int lag2 = arm_l_out2 > c->p.arm_min_l ? arm_l_out2 : c->p.arm_min_l;
         if (on && (!c->vm2 || lag2 != c->arms2_lag)) {
@@ -802,11 +864,20 @@ sm_status sm_cbca_double_config(sm_ctx* c, int32_t enable, int32_t arm_l2, int32
     c->dw_ct = arm_c_thresh2;
     c->dw_ct_out = arm_c_thresh_out2;
     c->dw_isum = dw_int_threshold(arm_len_thres);
+    c->dw_thres = arm_len_thres;
     return SM_OK;
 }
 
+sm_status sm_cbca_double_config(sm_ctx* c, int32_t enable, int32_t arm_l2, int32_t arm_l_out2, int32_t arm_c_thresh2,
+                                int32_t arm_c_thresh_out2, float arm_len_thres) {
+    // calArms divides window 1's arm limits by the level's scale too (cpp:5367-5371)
+    return on_levels(c, [&](sm_ctx* q, int l, bool dry) {
+        return dw_config_one(q, enable, arm_l2 >> l, arm_l_out2 >> l, arm_c_thresh2, arm_c_thresh_out2, arm_len_thres, dry);
+    });
+}
+
 sm_status sm_get_cbca_dw_mask(sm_ctx* c, uint8_t* dst) {
-    sm_status s = check(c);
+    sm_status s = check_any(c);
     if (s) return s;
     if (!dst) return fail(c, SM_EINVAL, "null dst");
     if (!c->dw_on || !c->dw_ran || c->stage < 2)
@@ -814,15 +885,15 @@ sm_status sm_get_cbca_dw_mask(sm_ctx* c, uint8_t* dst) {
     return download_sync(c, dst, c->dw_mask, c->npix);
 }
 
-sm_status sm_cbca_intersect_config(sm_ctx* c, int32_t intersect) {
-    if (!c) return SM_EINVAL;
+static sm_status intersect_config_one(sm_ctx* c, int32_t intersect, bool dry) {
     // the arguments are checked before any device call, so on a machine without a GPU too
     if (c->p.aggregation != SM_AGG_CBCA)
         return fail(c, SM_EINVAL, "sm_cbca_intersect_config: the context's aggregation is not SM_AGG_CBCA");
     if (intersect != 0 && intersect != 1) return fail(c, SM_EINVAL, "intersect must be 0 or 1 (cbca_intersect)");
+    if (dry) return SM_OK;
     const bool off = intersect == 0 && c->st != nullptr;
     if (c->st) {   // a live context: nothing queued may still run under the old setting
-        sm_status s = check(c);
+        sm_status s = check_any(c);
         if (s) return s;
         if (off && (!c->ni_tmp || !c->ni_area)) {
             HIP_TRY(c, hipStreamSynchronize(c->st));
@@ -840,8 +911,12 @@ sm_status sm_cbca_intersect_config(sm_ctx* c, int32_t intersect) {
     return SM_OK;
 }
 
+sm_status sm_cbca_intersect_config(sm_ctx* c, int32_t intersect) {
+    return on_levels(c, [&](sm_ctx* q, int, bool dry) { return intersect_config_one(q, intersect, dry); });
+}
+
 sm_status sm_get_cbca_area(sm_ctx* c, int32_t view, int32_t* dst) {
-    sm_status s = check(c);
+    sm_status s = check_any(c);
     if (s) return s;
     if (!dst) return fail(c, SM_EINVAL, "null dst");
     if (view < 0 || view >= n_views(c->p)) return fail(c, SM_EINVAL, "view must be 0, or 1 with do_refine");
@@ -852,7 +927,7 @@ sm_status sm_get_cbca_area(sm_ctx* c, int32_t view, int32_t* dst) {
 
 sm_status sm_refine_ext_config(sm_ctx* c, int32_t do_pkr, float pkr_ratio, int32_t disp_pkr, int32_t do_bg_ipol,
                                int32_t bg_ipl_depth, int32_t do_subpixel, int32_t se_mode) {
-    if (!c) return SM_EINVAL;
+    if (sm_status r = refuse_level(c)) return r;
     // the arguments are checked before any device call, so on a machine without a GPU too
     if (!c->p.do_refine) return fail(c, SM_EINVAL, "sm_refine_ext_config: the context has do_refine = 0 (refine() never runs)");
     if (!std::isfinite(pkr_ratio)) return fail(c, SM_EINVAL, "pkr_ratio must be finite (ratio_PKR)");
@@ -928,7 +1003,7 @@ static sm_status da_alloc(sm_ctx* c) {
 
 sm_status sm_refine_da_config(sm_ctx* c, int32_t on, int32_t canny_low, int32_t canny_high, int32_t blur_side,
                               int32_t blur_centre) {
-    if (!c) return SM_EINVAL;
+    if (sm_status r = refuse_level(c)) return r;
     // the arguments are checked before any device call, so on a machine without a GPU too
     if (!c->p.do_refine) return fail(c, SM_EINVAL, "sm_refine_da_config: the context has do_refine = 0 (refine() never runs)");
     if (c->p.optimization == SM_OPT_SO)
@@ -1093,5 +1168,88 @@ sm_status sm_div_area_check(sm_ctx* c, int32_t exp2, int32_t bmax, uint64_t* mis
     *mismatches = h;
     return SM_OK;
 }
+
+// ---- the cross-scale pyramid inside sm_run ---------------------------------------------------
+
+// level `l`'s parameters from level l - 1's (main_.cpp:138-148; calArms' scale, cpp:5367-5371): the image halves,
+// rounding up; maxdisp / 2 + 1; the arm limits are level 0's divided by 2^l.  A level only builds and aggregates
+// its volumes: optimization "", one stream, no placement trials.
+static sm_params level_params(const sm_params& p0, const sm_params& prev, int l) {
+    sm_params p = prev;
+    p.rows = (prev.rows + 1) / 2;
+    p.cols = (prev.cols + 1) / 2;
+    p.num_disparities = (prev.num_disparities - 1) / 2 + 2;
+    p.arm_l = p0.arm_l >> l;
+    p.arm_l_out = p0.arm_l_out >> l;
+    p.optimization = SM_OPT_WTA;
+    p.placement_trials = 0;
+    p.num_streams = 1;
+    p.sub_batch = 0;
+    return p;
+}
+
+extern "C++" sm_status pyr_sync_schedule(sm_ctx* c) {
+    for (sm_ctx* q : c->levels) {
+        q->nstreams = c->nstreams;   // (one AWS weight band per stream the owner's groups run on)
+        sm_status s = aws_alloc_bands(q);
+        if (s) return fail(c, s, "pyramid level " + std::to_string(q->level) + ": " + q->err);
+    }
+    return SM_OK;
+}
+
+sm_status sm_pyramid_config(sm_ctx* c, int32_t py_lvl) {
+    sm_status s = refuse_level(c);
+    if (s) return s;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (py_lvl < 1 || py_lvl > sm::kMaxPyr) return fail(c, SM_EINVAL, "PY_LVL must be in [1, 8]");
+    std::vector<sm_params> lp(1, c->p);
+    for (int l = 1; l < py_lvl; l++) {
+        lp.push_back(level_params(c->p, lp[l - 1], l));
+        std::string why;
+        if (validate(lp[l], why) == SM_OK && lp[l].aggregation == SM_AGG_BF &&
+            (lp[l].rows < c->bf_kv / 2 + 1 || lp[l].cols < c->bf_ku / 2 + 1))
+            why = "aggregation BF: the window (sm_bf_config) does not fit the image";
+        if (!why.empty())
+            return fail(c, SM_EINVAL, "PY_LVL " + std::to_string(py_lvl) + ": pyramid level " + std::to_string(l) + " (" +
+                                          std::to_string(lp[l].rows) + " x " + std::to_string(lp[l].cols) + "): " + why);
+    }
+    if (!c->st) return SM_OK;   // (no live context: nothing to create)
+    if ((s = check(c))) return s;
+    if (py_lvl == 1 + (int)c->levels.size()) return SM_OK;
+    drain(c);
+    destroy_levels(c);
+    if (const char* e = getenv("SM_PYR_AB")) {
+        c->pyr_ab_old = strstr(e, "old_solve") != nullptr;
+        c->pyr_ab_loop = strstr(e, "loop_down") != nullptr;
+    }
+    for (int l = 1; l < py_lvl && !s; l++) {
+        sm_ctx* q = nullptr;
+        s = create_ctx(&q, &lp[l], c->device, c, l);
+        if (q) c->levels.push_back(q);
+        // the owner's aggregation-side settings (the *_config calls made before this one)
+        if (!s && c->p.aggregation == SM_AGG_AWS) s = aws_config_one(q, c->aws_rv, c->aws_ru, c->aws_gamma, false);
+        if (!s && c->p.aggregation == SM_AGG_BF) s = bf_config_one(q, c->bf_kv, c->bf_ku, false);
+        if (!s && c->p.aggregation == SM_AGG_GFNL) s = gfnl_config_one(q, c->gfnl_thresh, false);
+        if (!s && c->dw_on) s = dw_config_one(q, 1, c->dw_l >> l, c->dw_l_out >> l, c->dw_ct, c->dw_ct_out, c->dw_thres, false);
+        if (!s && c->ni_on) s = intersect_config_one(q, 0, false);
+        if (s) c->err = "pyramid level " + std::to_string(l) + ": " + (q ? q->err : std::string("out of host memory"));
+    }
+    if (!s) s = pyr_sync_schedule(c);
+    if (s) {   // back to PY_LVL 1, with nothing kept
+        const std::string why = c->err;
+        destroy_levels(c);
+        (void)hipGetLastError();
+        c->err = why;
+        return s;
+    }
+    return SM_OK;
+}
+
+sm_ctx* sm_pyramid_level(sm_ctx* c, int32_t level) {
+    if (!c || c->owner || level < 0 || level > (int)c->levels.size()) return nullptr;
+    return level == 0 ? c : c->levels[level - 1];
+}
+
+int32_t sm_pyramid_levels(const sm_ctx* c) { return c ? 1 + (int32_t)c->levels.size() : 0; }
 
 }  // extern "C"

@@ -104,6 +104,7 @@ struct sm_ctx {
     bool dw_on = false;
     int dw_l = 23, dw_l_out = 23, dw_ct = 30, dw_ct_out = 0;
     int dw_isum = 45;              // arm_Mask = sum of the nine arm maxima < dw_isum: armLthres' integer form (dw_int_threshold)
+    float dw_thres = 5.0f;         // armLthres as given (a new pyramid level is configured from it)
     uint8_t* arms2 = nullptr;      // [cap][2 views][2 planes][npix] u32
     uint8_t* arms2_alloc = nullptr;
     size_t arms2_bytes = 0;
@@ -155,6 +156,7 @@ struct sm_ctx {
     int nl_set = 0;                         // record / table set the next run_nl takes (double-buffered)
     hipStream_t nl_st = nullptr;        // NL front (median, edge weights, spanning trees, tree walk)
     hipEvent_t nl_ev_set[2] = {nullptr, nullptr};   // the last filter reading each record / table set (group's stream)
+    hipEvent_t nl_ev_in = nullptr;      // a pyramid level: the group's stream has written the level's images (run_nl)
     // pipelined NL front (sm_run with NL + SGM, one view): the call's prep and cost volume also run
     // on nl_st, into a cost volume and penalty flags of the call's set, so they overlap the
     // previous call's filter and SGM on the main stream
@@ -166,6 +168,15 @@ struct sm_ctx {
     double* nl_val = nullptr;   // [cap][nvol]
     double* nl_oup = nullptr;   // [cap][npix] the ones channel: up sums
     double* nl_ofin = nullptr;  // [cap][npix] final sums
+    // the cross-scale pyramid inside sm_run (sm_pyramid_config): the contexts of levels 1 .. PY_LVL - 1, owned by
+    // level 0's.  A level context is an ordinary context (sm_create's buffers for its own size, optimization "")
+    // whose stages sm_run drives with the owner's groups, on the owner's streams; its launches are profiled in
+    // the owner's table as name@level; nl_st is the owner's (borrowed).  Its own main stream serves the getters
+    std::vector<sm_ctx*> levels;
+    sm_ctx* owner = nullptr;    // set in a level context
+    int level = 0;
+    bool pyr_ab_old = false;    // A/B switches of tools/bench_pyramid.py (SM_PYR_AB, read by sm_pyramid_config): the
+    bool pyr_ab_loop = false;   // staged SolveAll kernel / one pyrDown launch per image instead of the batch forms
     int n_loaded = 0;
     int stage = 0;              // 0 none, 1 images, 2 cost+agg, 3 solve_all, 4 optimized, 5 refined
     float lut_a[1024], lut_b[1024];
@@ -235,22 +246,25 @@ inline sm_status hip_fail(sm_ctx* c, hipError_t e, const char* where) {
 hipEvent_t get_event(sm_ctx* c);
 int kernel_id(sm_ctx* c, const char* name, double bytes);
 
-// Brackets one launch on stream `st` with events when profiling is on.
+// Brackets one launch on stream `st` with events when profiling is on.  A pyramid level's launches go into its
+// owner's table, as name@level.
 template <typename F>
 sm_status timed(sm_ctx* c, hipStream_t st, const char* name, double bytes, F&& launch) {
     ProfRec r{-1, nullptr, nullptr};
-    if (c->prof) {
-        r.kernel = kernel_id(c, name, bytes);
-        r.start = get_event(c);
-        r.stop = get_event(c);
+    sm_ctx* pc = c->owner ? c->owner : c;
+    if (pc->prof) {
+        r.kernel = c->owner ? kernel_id(pc, (std::string(name) + "@" + std::to_string(c->level)).c_str(), bytes)
+                            : kernel_id(pc, name, bytes);
+        r.start = get_event(pc);
+        r.stop = get_event(pc);
         if (r.start) hipEventRecord(r.start, st);
     }
     launch();
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(c, e, name);
-    if (c->prof && r.start && r.stop) {
+    if (pc->prof && r.start && r.stop) {
         hipEventRecord(r.stop, st);
-        c->recs.push_back(r);
+        pc->recs.push_back(r);
     }
     return SM_OK;
 }
@@ -367,11 +381,23 @@ inline sm_status wait_copy(sm_ctx* c) {
     return SM_OK;
 }
 
-inline sm_status check_nojoin(sm_ctx* c) {
+// A pyramid level context handed out by sm_pyramid_level takes the volume / arm / census / area / mask getters only.
+inline sm_status refuse_level(sm_ctx* c) {
+    if (!c) return SM_EINVAL;
+    if (c->owner) return fail(c, SM_ESTATE, "a pyramid level context (sm_pyramid_level) takes only the getters; configure and run its owner");
+    return SM_OK;
+}
+
+inline sm_status set_device(sm_ctx* c) {
     if (!c) return SM_EINVAL;
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail(c, e, "hipSetDevice");
     return SM_OK;
+}
+
+inline sm_status check_nojoin(sm_ctx* c) {
+    sm_status s = refuse_level(c);
+    return s ? s : set_device(c);
 }
 
 // Orders the main stream after everything queued on side stream i (one event).  A failed join drains the side
@@ -395,6 +421,14 @@ inline sm_status join_all(sm_ctx* c) {
 
 inline sm_status check(sm_ctx* c) {
     sm_status s = check_nojoin(c);
+    if (s) return s;
+    return join_all(c);
+}
+
+// check() for the calls a level context takes too: the getters above, and the per-context halves of the
+// aggregation-side *_config calls, which the owner's call runs on every level
+inline sm_status check_any(sm_ctx* c) {
+    sm_status s = set_device(c);
     if (s) return s;
     return join_all(c);
 }
@@ -439,6 +473,10 @@ sm_status run_other_agg(sm_ctx* c, const Group& G, bool solve_all = false, float
 bool agg_scale_fused(const sm_params& p, int view);
 const uint16_t* aws_tables();
 sm_status aws_alloc_bands(sm_ctx* c);
+
+// sm_capi.cpp
+bool pyr_weights(int L, float lam, float* w);     // row 0 of SolveAll's inverted matrix; false: singular
+sm_status pyr_sync_schedule(sm_ctx* c);           // the levels follow the owner's stream count (per-lane scratch)
 
 // sm_run.cpp
 sm_status apply_schedule(sm_ctx* c, int num_streams, int sub_batch);

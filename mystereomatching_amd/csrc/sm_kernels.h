@@ -319,6 +319,12 @@ void launch_so(const SoArgs& a, hipStream_t st);
 void launch_pyr_down(const uint8_t* src, uint8_t* dst, int rows, int cols, int ch, hipStream_t st);
 void launch_pyr_down_f32(const float* src, float* dst, int rows, int cols, hipStream_t st);
 void launch_solve_all_pyr(const PyrArgs& a, hipStream_t st);
+// the batch path's forms (sm_run with a pyramid): pyrDown of a group's nimg = 2 n images, colour [nimg][rows][cols][3]
+// and gray [nimg][rows][cols], in one launch; SolveAll with a 2 x 2 block of level-0 pixels per thread group
+// (same sums as launch_solve_all_pyr, bit for bit)
+void launch_pyr_down_batch(const uint8_t* src_bgr, const uint8_t* src_gray, uint8_t* dst_bgr, uint8_t* dst_gray, int rows,
+                           int cols, int nimg, hipStream_t st);
+void launch_solve_all_pyr_batch(const PyrArgs& a, hipStream_t st);
 void launch_median3(const int16_t* src, int16_t* dst, int n, int H, int W, hipStream_t st);
 int sgm_k_for(int D);
 

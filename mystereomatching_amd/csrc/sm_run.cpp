@@ -83,7 +83,82 @@ struct Schedule {
     bool early;    // group k + 1 starts after group k's first CBCA sweep (else after its aggregation)
     bool start;    // the groups start from a joined state
     bool nl_pipe;  // prep, cost volume and trees on the NL front stream (run_nl)
+    int levels;    // PY_LVL (sm_pyramid_config)
+    float pw[sm::kMaxPyr];   // levels > 1: SolveAll's weight of every level (pyr_weights)
 };
+
+// The coarse levels of G's pairs, on G's stream (sm_pyramid_config; main_.cpp:138-156): every level's input
+// images from the level above -- colour and gray, both views, filtered themselves -- in one launch per level,
+// then prep, cost volume(s) and aggregation of levels PY_LVL - 1 .. 1 through the stage drivers, with the
+// group's descriptor on the level's context.  The pyrDown launches come first: they are the coarse levels'
+// only readers of level 0's input images, which the next call's asynchronous upload may overwrite once the
+// group's in_ev is recorded (after level 0's cost volume or first sweep, later on this stream).
+static sm_status run_coarse_levels(sm_ctx* c, const Group& G) {
+    sm_status s = SM_OK;
+    const int L = 1 + (int)c->levels.size();
+    for (int l = 1; l < L && !s; l++) {
+        sm_ctx* q = c->levels[l - 1];
+        const sm_ctx* up = l == 1 ? c : c->levels[l - 2];
+        const Group S = at(up, G.off, G.n, G.st, G.lane), Q = at(q, G.off, G.n, G.st, G.lane);
+        const int H = up->p.rows, W = up->p.cols;
+        const double bytes = (double)G.n * 2 * 4 * (up->npix + q->npix);
+        s = timed(q, G.st, "pyr_down", bytes, [&] {
+            if (c->pyr_ab_loop) {   // (A/B: the staged API's launch per image)
+                for (int i = 0; i < 2 * G.n; i++) {
+                    sm::launch_pyr_down(S.bgr + (size_t)i * up->npix * 3, Q.bgr + (size_t)i * q->npix * 3, H, W, 3, G.st);
+                    sm::launch_pyr_down(S.gray + (size_t)i * up->npix, Q.gray + (size_t)i * q->npix, H, W, 1, G.st);
+                }
+            } else {
+                sm::launch_pyr_down_batch(S.bgr, S.gray, Q.bgr, Q.gray, H, W, 2 * G.n, G.st);
+            }
+        });
+    }
+    for (int l = L - 1; l >= 1 && !s; l--) {
+        sm_ctx* q = c->levels[l - 1];
+        const Group Q = at(q, G.off, G.n, G.st, G.lane);
+        if ((s = run_prep(q, Q))) break;
+        if ((s = run_cost(q, 0, Q))) break;
+        if (right_view(q->p) && (s = run_cost(q, 1, Q))) break;
+        if (q->p.aggregation == SM_AGG_CBCA)
+            for (int v = 0; v < n_views(q->p) && !s; v++) s = run_cbca(q, v, false, 1.0f, Q);
+        if (!s) s = run_other_agg(q, Q);
+    }
+    if (s)
+        for (sm_ctx* q : c->levels)
+            if (!q->err.empty()) {
+                c->err = "pyramid level " + std::to_string(q->level) + ": " + q->err;
+                q->err.clear();
+                break;
+            }
+    return s;
+}
+
+// Cross-scale SolveAll (cpp:2179-2203) of G's pairs into level 0's volume(s), on G's stream
+static sm_status run_solve_all_pyr(sm_ctx* c, const Group& G, const Schedule& S) {
+    sm::PyrArgs a{};
+    a.levels = S.levels;
+    a.n = G.n;
+    for (int l = 0; l < S.levels; l++) {
+        const sm_ctx* q = l ? c->levels[l - 1] : c;
+        a.H[l] = q->p.rows;
+        a.W[l] = q->p.cols;
+        a.D[l] = q->p.num_disparities;
+        a.w[l] = S.pw[l];
+    }
+    for (int v = 0; v < n_views(c->p); v++) {
+        a.vm[0] = G.vm(v);
+        for (int l = 1; l < S.levels; l++) {
+            const sm_ctx* q = c->levels[l - 1];
+            a.vm[l] = (v == 0 ? q->vm0 : q->vm1) + (size_t)G.off * q->nvol;
+        }
+        sm_status s = timed(c, G.st, Group::name("solve_all_pyr", v), (double)G.n * c->nvol * 8.0, [&] {
+            if (c->pyr_ab_old) sm::launch_solve_all_pyr(a, G.st);   // (A/B: the staged API's kernel)
+            else sm::launch_solve_all_pyr_batch(a, G.st);
+        });
+        if (s) return s;
+    }
+    return SM_OK;
+}
 
 // Group k of an sm_run: every stage of G's pairs on G's stream, with the events that tie it to the other
 // groups, to the asynchronous map copy and to the next asynchronous upload.
@@ -92,6 +167,8 @@ static sm_status run_group(sm_ctx* c, Group G, int k, const Schedule& S) {
     sm_status s = SM_OK;
     if (ns > 1 && k > 0 && S.start) HIP_TRY(c, hipStreamWaitEvent(G.st, c->ev_stagger[(k - 1) % 8], 0));
     Group Go = G;   // what the optimiser reads
+    const bool pyr = S.levels > 1;   // SolveAll is then the cross-scale pass below, not a weight fused into a last store
+    if (pyr && (s = run_coarse_levels(c, G))) return s;
     const int set = c->nl_set;   // (NL: the record / table set this call's run_nl takes)
     if (S.nl_pipe) {
         if ((s = nl_open(c, G.st))) return s;
@@ -102,7 +179,7 @@ static sm_status run_group(sm_ctx* c, Group G, int k, const Schedule& S) {
         if ((s = run_prep(c, G))) return s;
         if ((s = run_cost(c, 0, G))) return s;
         if (right_view(c->p) && (s = run_cost(c, 1, G))) return s;
-        if ((s = run_other_agg(c, G, true, S.w))) return s;   // SolveAll fused into the GF / NL output stores
+        if ((s = run_other_agg(c, G, !pyr, S.w))) return s;   // SolveAll fused into the GF / NL output stores
     }
     // the group's input images are read by prep and the cost volume only (CBCA + SGM, no refinement:
     // the pipelined form): the next call's async upload may overwrite them once ev_in[k] is recorded --
@@ -117,11 +194,12 @@ static sm_status run_group(sm_ctx* c, Group G, int k, const Schedule& S) {
     if (ns > 1 && S.early) G.stagger_ev = c->ev_stagger[k % 8];   // run_cbca records it after its first sweep
     for (int v = 0; v < n_views(c->p) && !S.nl_pipe; v++) {
         if (c->p.aggregation == SM_AGG_CBCA && cbca_iters(c) > 0)
-            s = run_cbca(c, v, true, S.w, G);   // SolveAll fused into the last pass
-        else if (!agg_scale_fused(c->p, v))
+            s = run_cbca(c, v, !pyr, S.w, G);   // SolveAll fused into the last pass
+        else if (!pyr && !agg_scale_fused(c->p, v))
             s = run_scale(c, v, S.w, G);      // (GF, FIF, AWS, BF, GFNL and NL's vm[0]: fused above)
         if (s) return s;
     }
+    if (pyr && (s = run_solve_all_pyr(c, G, S))) return s;
     // the maps are written from here on: an asynchronous copy of the previous run's maps
     // (sm_download_disp_async) must be done reading them
     // (a split copy: ev_copy covers pairs [0, copy_g) only; a group reaching past them -- the
@@ -178,7 +256,9 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     // (a different split of the pairs would let the groups of two calls share a pair: join first)
     if ((!S.piped || g != c->pipe_g) && (s = join_all(c))) return s;
     S.start = !(S.piped && c->pipe_live);
-    S.nl_pipe = c->nl_pipe && g >= n && ns == 1;
+    S.levels = 1 + (int)c->levels.size();
+    if (S.levels > 1 && !pyr_weights(S.levels, reg_lambda, S.pw)) return fail(c, SM_EINVAL, "singular regularisation matrix");
+    S.nl_pipe = c->nl_pipe && g >= n && ns == 1 && S.levels == 1;
     if (ns > 1 && S.start) {   // the side streams start after everything queued so far on the main stream
         if ((s = use_event(c, c->ev_start))) return s;
         HIP_TRY(c, hipEventRecord(c->ev_start, c->st));
@@ -202,6 +282,10 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
     if (s) return s;
     c->stage = c->p.do_refine ? 5 : 4;
     c->rx_vol_ok = true;
+    for (sm_ctx* q : c->levels) {   // (what the getters on sm_pyramid_level's contexts check)
+        q->stage = 2;
+        q->n_loaded = n;
+    }
     if (disp_out) return sm_download_disp(c, n, disp_out);
     return SM_OK;
 }
@@ -435,6 +519,7 @@ sm_status sm_set_schedule(sm_ctx* c, int32_t num_streams, int32_t sub_batch) {
     // groups are ordered after it whichever streams they use)
     if ((s = apply_schedule(c, num_streams, sub_batch))) return s;
     if ((s = aws_alloc_bands(c))) return s;
+    if ((s = pyr_sync_schedule(c))) return s;
     c->p.num_streams = num_streams;
     c->p.sub_batch = sub_batch;
     return SM_OK;

@@ -63,9 +63,17 @@ static sm_status run_gf(sm_ctx* c, int view, const Group& G, bool solve_all, flo
 // only for the filter that last read the set it writes.
 // nl_open creates that stream on first use, with the sets' events, recorded once on `st` (the
 // stream of the group that runs NL first) so that the first waits find them complete.
+// A pyramid level context takes its owner's front stream: the front's work space (spanning trees, tree walk) is
+// one per context, and one stream orders the levels' and the groups' fronts as it orders the groups' alone.
 sm_status nl_open(sm_ctx* c, hipStream_t st) {
     if (c->nl_st) return SM_OK;
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->nl_st, hipStreamNonBlocking));
+    if (c->owner) {
+        sm_status s = nl_open(c->owner, st);
+        if (s) return fail(c, s, c->owner->err);
+        c->nl_st = c->owner->nl_st;
+    } else {
+        HIP_TRY(c, hipStreamCreateWithFlags(&c->nl_st, hipStreamNonBlocking));
+    }
     for (hipEvent_t* ev : {c->nl_ev_set, c->nl_ev_opt})
         for (int i = 0; i < 2; i++) {
             sm_status s = use_event(c, ev[i]);
@@ -99,6 +107,11 @@ sm_status run_nl(sm_ctx* c, const Group& G, bool solve_all, float w, const Group
     Group F = G;   // the front's launches (and their profiling events) go to nl_st
     F.st = c->nl_st;
     if (front) F = *front;
+    if (c->owner) {   // a level's images are this call's pyrDown output, written on the group's stream
+        if ((s = use_event(c, c->nl_ev_in))) return s;
+        HIP_TRY(c, hipEventRecord(c->nl_ev_in, G.st));
+        HIP_TRY(c, hipStreamWaitEvent(F.st, c->nl_ev_in, 0));
+    }
     const int set = c->nl_set;
     c->nl_set ^= 1;
     int* I = c->nl_ints + (size_t)set * 4 * slot;

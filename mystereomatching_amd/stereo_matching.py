@@ -381,6 +381,8 @@ class StereoBatch:
         refine_ext = overrides.pop("refine_ext", None)
         # refine()'s discontinuity adjustment (sm_refine_da_config): refine_da is a dict of refine_da_config's arguments
         refine_da = overrides.pop("refine_da", None)
+        # the cross-scale pyramid inside run() (sm_pyramid_config): py_lvl = PY_LEV of main_.cpp:131, applied last
+        py_lvl = int(overrides.pop("py_lvl", 1))
         p = _capi.default_params(max_disp, rows, cols, **overrides)
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
@@ -402,6 +404,8 @@ class StereoBatch:
             self.refine_ext_config(**dict(refine_ext))
         if refine_da:
             self.refine_da_config(**dict(refine_da))
+        if py_lvl != 1:
+            self.pyramid_config(py_lvl)
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -554,6 +558,47 @@ class StereoBatch:
         out = np.empty(self.shape[:2], np.int32)
         st = self._lib.sm_get_cbca_area(self._ctx, int(view), _capi.ptr(out))
         _capi.check(self._lib, self._ctx, st, "get_cbca_area")
+        return out
+
+    def pyramid_config(self, py_lvl: int = 1):
+        """sm_pyramid_config: run() builds py_lvl pyramid levels per pair (pyrDown'ed inputs, halved disparity range
+        and arm limits) and SolveAll combines them into level 0 before the optimiser; 1 = no pyramid."""
+        _capi.check(self._lib, self._ctx, self._lib.sm_pyramid_config(self._ctx, int(py_lvl)), "pyramid_config")
+
+    @property
+    def pyramid_levels(self) -> int:
+        return int(self._lib.sm_pyramid_levels(self._ctx))
+
+    def _pyramid_level(self, level: int):
+        """(borrowed context, (rows, cols, num_disparities)) of pyramid level `level`, after synchronize()."""
+        ctx = self._lib.sm_pyramid_level(self._ctx, int(level))
+        if not ctx:
+            raise ValueError(f"pyramid level {level} out of range (py_lvl = {self.pyramid_levels})")
+        self.synchronize()
+        h, w, d = self.shape
+        for _ in range(int(level)):
+            h, w, d = (h + 1) // 2, (w + 1) // 2, (d - 1) // 2 + 2
+        return C.c_void_p(ctx), (h, w, d)
+
+    def pyramid_level_volume(self, level: int, view: int = 0) -> np.ndarray:
+        """The first pair's vm[view] of pyramid level `level` after the last run (level 0: the combined volume)."""
+        ctx, (h, w, d) = self._pyramid_level(level)
+        out = np.empty((h, w, d), np.float32)
+        _capi.check(self._lib, ctx, self._lib.sm_get_volume(ctx, int(view), _capi.ptr(out)), "pyramid_level_volume")
+        return out
+
+    def pyramid_level_arms(self, level: int, view: int = 0) -> np.ndarray:
+        """The first pair's arms HVL[view] [H_s][W_s][4] of pyramid level `level` after the last run."""
+        ctx, (h, w, _) = self._pyramid_level(level)
+        out = np.empty((h, w, 4), np.uint16)
+        _capi.check(self._lib, ctx, self._lib.sm_get_arms(ctx, int(view), _capi.ptr(out)), "pyramid_level_arms")
+        return out
+
+    def pyramid_level_census(self, level: int, view: int = 0) -> np.ndarray:
+        """The first pair's census codes [H_s][W_s][2] (uint64) of pyramid level `level` after the last run."""
+        ctx, (h, w, _) = self._pyramid_level(level)
+        out = np.empty((h, w, 2), np.uint64)
+        _capi.check(self._lib, ctx, self._lib.sm_get_census(ctx, int(view), _capi.ptr(out)), "pyramid_level_census")
         return out
 
     def refine_ext_config(self, do_pkr: bool = False, pkr_ratio: float = _capi.REFINE_EXT_DEFAULTS[0],

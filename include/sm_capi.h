@@ -44,6 +44,11 @@
  *   sm_refine_da_config <- static switch Do_discontinuityAdjust (h:78), the literals of cpp:6063-6064
  *                         (discontinuityAdjust cpp:6057-6136)
  *   sm_get_da_edges    <- discontinuityAdjust's local disp_E after Canny (cpp:6064)
+ *   sm_refine_outlier_config <- the commented alternatives of refine() at cpp:1367 and cpp:1408,
+ *                         Parameters::DISP_MIS (h:217), interpolateType (h:178, 310)
+ *                         (LRConsistencyCheck cpp:2284-2335; RV_combine_BG cpp:7146-7216 with
+ *                          cal_histogram_for_HV cpp:6830-6862, backgroundInterpolateCore cpp:6964-7043)
+ *   sm_get_lrc_mask    <- member LRC_Err_Mask as LRConsistencyCheck leaves it (cpp:2291-2309)
  *   sm_get_volume / sm_set_volume <- public member vm[view]       stereoMatching.h:2720
  *   sm_get_arms        <- public member HVL[view]                    stereoMatching.h:2717
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
@@ -304,7 +309,7 @@ SM_API sm_status sm_run(sm_ctx* ctx, int32_t n, float reg_lambda, int16_t* disp_
  * sm_aws_config, sm_bf_config, sm_gfnl_config, sm_cbca_double_config (arm_l2 and arm_l_out2 divided by 2^s) and
  * sm_cbca_intersect_config apply to every level, whichever order they and this call come in; a level that cannot
  * take a setting fails that call with the level named and every level unchanged.  sm_vmtop_config,
- * sm_refine_ext_config and sm_refine_da_config concern level 0 only.  The staged calls keep their contracts
+ * sm_refine_ext_config, sm_refine_da_config and sm_refine_outlier_config concern level 0 only.  The staged calls keep their contracts
  * (sm_solve_all refuses py_lev != 1; sm_solve_all_pyr takes one context per level).
  * Checked before any device call: py_lvl outside [1, 8] and a level that sm_create would refuse (rows or cols < 2,
  * an aggregation's minimum size, ..) are SM_EINVAL with the level and its reason in sm_last_error.  On a live
@@ -478,7 +483,8 @@ typedef enum sm_se_mode {
  * do_pkr with num_disparities < 2 (the reference's second search writes slot -1), and do_pkr or do_subpixel with
  * optimization "so" (the reference's so rewrites vm in place, cpp:6299; this back end keeps a trace instead);
  * the arguments are checked without a device.  Do_discontinuityAdjust is built (sm_refine_da_config).  Not built:
- * Do_WM (reads a mask the shipped LR check never writes) and Do_cbbi (needs floodFill and theRNG()). */
+ * Do_WM (reads a mask the shipped LR check never writes; with sm_refine_outlier_config's classify the mask exists,
+ * but the stage still indexes a histogram with negative disparities) and Do_cbbi (needs floodFill and theRNG()). */
 SM_API sm_status sm_refine_ext_config(sm_ctx* ctx, int32_t do_pkr, float pkr_ratio, int32_t disp_pkr, int32_t do_bg_ipol,
                                       int32_t bg_ipl_depth, int32_t do_subpixel, int32_t se_mode);
 /* Pair 0's PKR_Err_Mask / float map SE of the last sm_refine / sm_run with the stage on: rows x cols bytes /
@@ -512,6 +518,43 @@ SM_API sm_status sm_refine_da_config(sm_ctx* ctx, int32_t on, int32_t canny_low,
 /* Pair 0's edge map (0 / 255) of the last sm_refine / sm_run with the stage on: rows x cols bytes.  SM_ESTATE
  * before that. */
 SM_API sm_status sm_get_da_edges(sm_ctx* ctx, uint8_t* dst);
+
+/* refine()'s outlier classification: two source switches of refine(), both off in the shipped build.
+ *   classify     LRConsistencyCheck (cpp:2284-2335, LOR = 0; the commented call at cpp:1367) instead of
+ *                LRConsistencyCheck_normal: with d = DP[0](v, u), a pixel fails when d < 0, u - d < 0 or
+ *                (float)|d - DP[1](v, u - d)| > lr_max_diff (the same test); a failed pixel gets mask byte 255 and
+ *                the label disp_mis (DISP_MIS = -48) if some d' in [0, min(num_disparities, u + 1)) has
+ *                DP[1](v, u - d') == d', else sm_params.disp_occ (DISP_OCC = -32); passing pixels keep their value
+ *                and get mask byte 0.  The DT-based counters, their cout lines and the imwrite are not reproduced.
+ *   rv_combine   RV_combine_BG (cpp:7146-7216; the commented call at cpp:1408) instead of every regionVote_my round,
+ *                under the same do_region_vote / region_vote_nums / rv_s / rv_ratio, Jacobi.  A hole (DP[0] < 0)
+ *                takes, by interpolate_type (Parameters::interpolateType): 0 the vote rv; 1 the background value
+ *                bg; 2 bg on a disp_occ hole, rv on a disp_mis hole; 3 on a disp_occ hole the smaller of rv and bg
+ *                (the one that is >= 0 if only one is), rv on a disp_mis hole.  rv is cal_histogram_for_HV
+ *                (cpp:6830-6862) over regionVote_my's region: -1 when validNum <= rv_s, else the first most frequent
+ *                disparity if (float)hist[most] / validNum > rv_ratio (a float division, a strict compare), else -1.
+ *                bg is backgroundInterpolateCore (cpp:6964-7043): the nearest value >= 0 within bg_ipl_depth columns
+ *                right and left on the row, the smaller of those found, else -1; the depth is
+ *                sm_refine_ext_config's bg_ipl_depth (1000 until that call), 0 finds nothing.  A result >= 0
+ *                replaces the hole, otherwise the hole keeps its value, label included.  Types 2 and 3 assign
+ *                nothing for a hole of neither class (DISP_PKR, or -1 without classify): the reference's `dp_`
+ *                (cpp:7158) outlives both loops, so such a hole takes the result of the nearest earlier hole of
+ *                either class in raster order within its pair and round (-1 before the first).  This is reproduced.
+ *                One deviation: a value >= num_disparities in the map (possible only through sm_set_disp) counts in
+ *                validNum and in no bin, where the reference indexes past its histogram.  The DT side channel is
+ *                not reproduced.
+ * Not sm_params fields (the struct keeps its size): both off by default, takes effect from the next sm_refine /
+ * sm_run; with a pyramid the call concerns level 0 only.  No stage here reads a volume, so the call is allowed with
+ * every optimiser, "so" included.  The maps are the same for every schedule, sub-batch and stream count; no launch
+ * count depends on the data and nothing is read back.  The mask and the scratch are allocated on the first enabling
+ * call (batch_capacity pairs).  SM_EINVAL, with the argument named in sm_last_error, on a context without do_refine,
+ * for disp_mis outside [-32767, -1] or equal to disp_occ, interpolate_type outside [0, 3], or a switch outside
+ * {0, 1}; the arguments are checked without a device. */
+SM_API sm_status sm_refine_outlier_config(sm_ctx* ctx, int32_t classify, int32_t disp_mis, int32_t rv_combine,
+                                          int32_t interpolate_type);
+/* Pair 0's LRC_Err_Mask (0 / 255) of the last sm_refine / sm_run with classify on: rows x cols bytes.  SM_ESTATE
+ * before that; SM_EINVAL for a null dst.  Both are decided without a device. */
+SM_API sm_status sm_get_lrc_mask(sm_ctx* ctx, uint8_t* dst);
 
 /* Diagnostics used by the parity tests. */
 /* CBCA's double window: pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where

@@ -347,6 +347,12 @@ class StereoMatching {
     // thresholds and the blur's 8.8 fixed-point taps are the literals of cpp:6063-6064 in the restated form
     inline static bool Do_discontinuityAdjust = false;
     inline static int da_canny_low = 20, da_canny_high = 60, da_blur_side = 84, da_blur_centre = 87;
+    // two source switches of refine() (sm_refine_outlier_config), commented out in the shipped build: LRC_CLASSIFY
+    // runs LRConsistencyCheck (cpp:1367, 2284-2335: failed pixels become DISP_OCC / DISP_MIS, the mask is left in
+    // LRC_Err_Mask) instead of LRConsistencyCheck_normal; RV_COMBINE_BG runs RV_combine_BG (cpp:1408, 7146-7216: a
+    // float ratio, the filler chosen per class by Parameters::interpolateType) instead of regionVote_my
+    inline static bool LRC_CLASSIFY = false;
+    inline static bool RV_COMBINE_BG = false;
     inline static bool Do_properIpol = true;       // h:76
     inline static bool Do_lastMedianBlur = true;   // h:80
     // `#define MY_GUIDE` (h:38, commented out in the shipped build) as a switch: false = GF runs
@@ -398,7 +404,9 @@ class StereoMatching {
         int errorThreshold = 1;               // h:225
         float LRmaxDiff = 0;                  // h:212
         int DISP_OCC = -2 * 16;               // h:216
+        int DISP_MIS = -3 * 16;               // h:217
         int DISP_PKR = -4 * 16;               // h:218
+        int interpolateType = 0;              // h:178, 310: RV_combine_BG's filler (RV_COMBINE_BG)
         int bgIplDepth = 1000;                // h:311
         int region_vote_nums = 2;             // h:306
         // Parameters(maxDisp, h, w, lamCen, lamG, M, lamc, ts, errCsvName, disSc) — main_.cpp:138
@@ -450,6 +458,10 @@ class StereoMatching {
         if (pkr_on_) {
             PKR_Err_Mask.create(h_, w_, CV_8U);
             check(sm_get_pkr_mask(ctx_, PKR_Err_Mask.ptr<uint8_t>()), "PKR_Err_Mask");
+        }
+        if (lrc_on_) {
+            LRC_Err_Mask.create(h_, w_, CV_8U);
+            check(sm_get_lrc_mask(ctx_, LRC_Err_Mask.ptr<uint8_t>()), "LRC_Err_Mask");
         }
         if (da_on_) {
             DA_Edge.create(h_, w_, CV_8U);
@@ -515,6 +527,7 @@ class StereoMatching {
     Mat SE;           // float H x W: refine()'s local SE after its median (cpp:1484-1490), with Do_subpixelEnhancement
     Mat PKR_Err_Mask; // uint8 H x W: calPKR's mask (cpp:1380), with Do_calPKR
     Mat DA_Edge;      // uint8 H x W: discontinuityAdjust's edge map (cpp:6064), with Do_discontinuityAdjust
+    Mat LRC_Err_Mask; // uint8 H x W: LRConsistencyCheck's mask, 0 / 255 (cpp:2291-2309), with LRC_CLASSIFY
     Mat I_mask[3];    // nonocc, all, disc (cpp:2073-2075)
     Parameters param_;
     int h_, w_, d_;
@@ -522,7 +535,7 @@ class StereoMatching {
 
    private:
     bool refine_on_ = false, csv_open_ = false;
-    bool pkr_on_ = false, se_on_ = false, da_on_ = false;
+    bool pkr_on_ = false, se_on_ = false, da_on_ = false, lrc_on_ = false;
     std::ostringstream csv_;
     std::vector<std::string> times_;
 
@@ -620,6 +633,11 @@ class StereoMatching {
         if (Do_refine && Do_discontinuityAdjust) {
             check(sm_refine_da_config(ctx_, 1, da_canny_low, da_canny_high, da_blur_side, da_blur_centre), "sm_refine_da_config");
             da_on_ = true;
+        }
+        if (Do_refine && (LRC_CLASSIFY || RV_COMBINE_BG)) {
+            check(sm_refine_outlier_config(ctx_, LRC_CLASSIFY ? 1 : 0, param.DISP_MIS, RV_COMBINE_BG ? 1 : 0, param.interpolateType),
+                  "sm_refine_outlier_config");
+            lrc_on_ = LRC_CLASSIFY;
         }
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }

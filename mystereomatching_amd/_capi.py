@@ -28,6 +28,8 @@ SE_REFERENCE, SE_FLOAT = 0, 1
 REFINE_EXT_DEFAULTS = (0.1, -64, 1000, SE_REFERENCE)
 # sm_refine_da_config's values: canny_low, canny_high, blur_side, blur_centre
 REFINE_DA_DEFAULTS = (20, 60, 84, 87)
+# sm_refine_outlier_config's values: disp_mis (DISP_MIS, h:217), interpolate_type (interpolateType, h:310)
+REFINE_OUTLIER_DEFAULTS = (-48, 0)
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
 
 
@@ -130,6 +132,8 @@ SIGNATURES = [
     ("sm_get_da_edges", C.c_int, [_P, _P]),
     ("sm_da_run_image", C.c_int, [_P, _P, C.c_int32, _P, _P, _P]),
     ("sm_set_da_edges", C.c_int, [_P, _P]),
+    ("sm_refine_outlier_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("sm_get_lrc_mask", C.c_int, [_P, _P]),
 ]
 
 _lib = None

@@ -111,6 +111,8 @@ def hip_compute_fn(max_disp: int, rows: int, cols: int, capacity: int, device: i
     run.download_subpixel = sb.download_subpixel  # type: ignore[attr-defined]
     # the first pair's edge map of the block last run (refine_da=dict(on=True, ...) among the overrides)
     run.get_da_edges = sb.get_da_edges  # type: ignore[attr-defined]
+    # the first pair's LR mask of the block last run (refine_outlier=dict(classify=True, ...) among the overrides)
+    run.get_lrc_mask = sb.get_lrc_mask  # type: ignore[attr-defined]
     # the runner may hand this function device tensors on its own GPU (no host round trip)
     run.device = torch.device("cuda", device)  # type: ignore[attr-defined]
     run.capacity = capacity  # type: ignore[attr-defined]

@@ -1042,6 +1042,38 @@ sm_status sm_get_da_edges(sm_ctx* c, uint8_t* dst) {
     return download_sync(c, dst, c->da_u8 + (size_t)sm::DA_EDGE * c->npix, c->npix);
 }
 
+sm_status sm_refine_outlier_config(sm_ctx* c, int32_t classify, int32_t disp_mis, int32_t rv_combine, int32_t interpolate_type) {
+    if (sm_status r = refuse_level(c)) return r;
+    // the arguments are checked before any device call, so on a machine without a GPU too
+    if (const char* why = outlier_config_error(c->p, classify, disp_mis, rv_combine, interpolate_type)) return fail(c, SM_EINVAL, why);
+    const bool live = c->st != nullptr;
+    if (live && (classify || rv_combine)) {
+        sm_status s = check(c);
+        if (s) return s;
+        const size_t cap = (size_t)c->cap;
+        if (classify && !c->oc_mask && (s = dalloc(c, &c->oc_mask, cap * c->npix))) return s;
+        if (rv_combine && !c->oc_cand && (s = dalloc(c, &c->oc_cand, cap * c->npix))) return s;
+        if (rv_combine && !c->oc_rowlast && (s = dalloc(c, &c->oc_rowlast, cap * (size_t)c->p.rows))) return s;
+    }
+    c->oc_classify = live && classify;
+    c->oc_rv = live && rv_combine;
+    c->oc_disp_mis = disp_mis;
+    c->oc_type = interpolate_type;
+    c->oc_ran = false;
+    return SM_OK;
+}
+
+sm_status sm_get_lrc_mask(sm_ctx* c, uint8_t* dst) {
+    // the argument and the state are checked before any device call, so on a machine without a GPU too
+    if (!c) return SM_EINVAL;
+    if (!dst) return fail(c, SM_EINVAL, "sm_get_lrc_mask: null dst");
+    if (!c->oc_classify || !c->oc_ran || c->stage < 5)
+        return fail(c, SM_ESTATE, "no mask yet (sm_refine_outlier_config with classify, then sm_refine / sm_run)");
+    sm_status s = check(c);
+    if (s) return s;
+    return download_sync(c, dst, c->oc_mask, c->npix);
+}
+
 sm_status sm_da_run_image(sm_ctx* c, const uint8_t* src, int32_t first_stage, uint8_t* out_eq, uint8_t* out_blur,
                           uint8_t* out_edges) {
     sm_status s = check(c);

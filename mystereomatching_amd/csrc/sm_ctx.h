@@ -141,6 +141,15 @@ struct sm_ctx {
     uint8_t* da_user = nullptr;    // [npix] sm_set_da_edges' map
     bool da_user_on = false;       // the next refine takes da_user for every pair instead of Canny's map
     bool da_ran = false;           // pair 0's DA_EDGE plane holds the last refine's edge map
+    // refine()'s outlier classification (sm_refine_outlier_config; sm_refine_oc.hip)
+    bool oc_classify = false;      // LRConsistencyCheck instead of LRConsistencyCheck_normal
+    bool oc_rv = false;            // RV_combine_BG instead of regionVote_my
+    int oc_disp_mis = -3 * 16;     // DISP_MIS (h:217)
+    int oc_type = 0;               // interpolateType (h:310)
+    uint8_t* oc_mask = nullptr;    // [cap][npix] LRC_Err_Mask
+    int16_t* oc_cand = nullptr;    // [cap][npix] the classified holes' results of a round (types 2, 3)
+    int16_t* oc_rowlast = nullptr; // [cap][rows] each row's last classified result
+    bool oc_ran = false;           // the last refine filled the mask
     // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -450,6 +459,7 @@ int cbca_lag(const sm_params& p);
 int cbca_lag2(const sm_ctx* c);
 int cbca_iters(const sm_ctx* c);
 bool refine_reads_volume(const sm_ctx* c);
+const char* outlier_config_error(const sm_params& p, int classify, int disp_mis, int rv_combine, int interpolate_type);
 int dw_int_threshold(float thres);
 bool cbca_div_safe(const sm_params& p, int k);
 sm_status validate(const sm_params& p, std::string& why);

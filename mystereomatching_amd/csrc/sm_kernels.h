@@ -432,4 +432,24 @@ void launch_da_edges(const DaArgs& a, hipStream_t st);
 void launch_da_dir(const DaArgs& a, const int16_t* src, int16_t* dst, hipStream_t st);   // dst = src
 void launch_da_adjust(const DaArgs& a, const int16_t* src, int16_t* dst, const float* vm, int D, hipStream_t st);
 
+// refine()'s outlier classification (sm_refine_oc.hip); pair-relative bases
+struct RvcArgs {
+    const int16_t* src;         // [n][H][W] the map before the round
+    int16_t* dst;               // [n][H][W] the copy the round fills
+    int16_t* cand;              // [n][H][W] types 2, 3: the classified holes' results, -32768 elsewhere (else null)
+    int16_t* rowlast;           // [n][H] types 2, 3: each row's last classified result, -32768 for none
+    const uint32_t* arms;       // [n][view][plane][H][W]: the left image's arms are read
+    int H, W, D, n;
+    int rv_s;                   // validNum <= rv_s votes -1
+    float rv_ratio;             // hist[most] / validNum > rv_ratio in float
+    int depth;                  // bgIplDepth >= 0
+    int type;                   // Parameters::interpolateType, 0 .. 3
+    int disp_occ, disp_mis;
+};
+// LRConsistencyCheck, LOR = 0: d0 is labelled in place, mask gets 0 / 255
+void launch_lr_classify(int16_t* d0, const int16_t* d1, uint8_t* mask, int n, int H, int W, int D, float maxdiff,
+                        int disp_occ, int disp_mis, hipStream_t st);
+void launch_rv_combine(const RvcArgs& a, hipStream_t st);          // D <= 1024 (sm_params' limit): 17 KiB of LDS
+void launch_rv_carry(const RvcArgs& a, hipStream_t st);            // types 2, 3, after launch_rv_combine
+
 }  // namespace sm

@@ -502,10 +502,21 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
     const sm_params& p = c->p;
     const int H = p.rows, W = p.cols;
     const double map = (double)G.n * c->npix * 2;
-    sm_status s = timed(c, G.st, "refine_lr_check", 3 * map,
-                        [&] { sm::launch_lr_check(G.disp, G.disp1, G.n, H, W, p.lr_max_diff, G.st); });
-    if (s) return s;
     const double np = (double)G.n * c->npix;
+    sm_status s;
+    if (c->oc_classify) {   // LRConsistencyCheck (cpp:2284-2335) in place of LRConsistencyCheck_normal (cpp:1364-1367)
+        uint8_t* mask = G.slice(c->oc_mask, c->npix);
+        // reads DP[0] and DP[1], writes the labels and the mask
+        s = timed(c, G.st, "refine_lr_classify", np * (2 + 2 + 2 + 1), [&] {
+            sm::launch_lr_classify(G.disp, G.disp1, mask, G.n, H, W, p.num_disparities, p.lr_max_diff, p.disp_occ,
+                                   c->oc_disp_mis, G.st);
+        });
+        c->oc_ran = true;
+    } else {
+        s = timed(c, G.st, "refine_lr_check", 3 * map,
+                  [&] { sm::launch_lr_check(G.disp, G.disp1, G.n, H, W, p.lr_max_diff, G.st); });
+    }
+    if (s) return s;
     if (c->rx_pkr) {   // calPKR + signDp_UsingPKR (cpp:1378-1383) on vm[0] as dispOptimize left it
         sm::PkrArgs a{};
         a.vm = G.vm0;
@@ -525,9 +536,34 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
     const uint32_t* arms = (const uint32_t*)G.arms;
     if (p.do_region_vote)
         for (int i = 0; i < p.region_vote_nums; i++) {
-            if ((s = timed(c, G.st, "refine_region_vote", 2 * map,
-                           [&] { sm::launch_region_vote(cur, nxt, arms, G.n, H, W, p.rv_s, p.rv_ratio, G.st); })))
+            if (c->oc_rv) {   // RV_combine_BG (cpp:7146-7216) in place of regionVote_my (cpp:1404-1408)
+                sm::RvcArgs a{};
+                a.src = cur;
+                a.dst = nxt;
+                const bool carry = c->oc_type >= 2;   // a hole of neither class takes the last classified hole's result
+                a.cand = carry ? G.slice(c->oc_cand, c->npix) : nullptr;
+                a.rowlast = carry ? G.slice(c->oc_rowlast, (size_t)H) : nullptr;
+                a.arms = arms;
+                a.H = H;
+                a.W = W;
+                a.D = p.num_disparities;
+                a.n = G.n;
+                a.rv_s = p.rv_s;
+                a.rv_ratio = p.rv_ratio;
+                a.depth = c->rx_depth;
+                a.type = c->oc_type;
+                a.disp_occ = p.disp_occ;
+                a.disp_mis = c->oc_disp_mis;
+                if ((s = timed(c, G.st, "refine_rv_combine", map * (carry ? 3 : 2), [&] { sm::launch_rv_combine(a, G.st); }))) return s;
+                // k_rv_row_last reads the scratch map and writes a value per row; k_rv_carry reads the map, the scratch
+                // map and the rows' values
+                if (carry && (s = timed(c, G.st, "refine_rv_carry", 3 * map + 4.0 * G.n * H, [&] { sm::launch_rv_carry(a, G.st); })))
+                    return s;
+            } else if ((s = timed(c, G.st, "refine_region_vote", 2 * map, [&] {
+                            sm::launch_region_vote(cur, nxt, arms, G.n, H, W, p.rv_s, p.rv_ratio, G.st);
+                        }))) {
                 return s;
+            }
             std::swap(cur, nxt);
         }
     if (p.do_proper_ipol)

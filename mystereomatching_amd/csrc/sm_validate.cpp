@@ -69,6 +69,18 @@ int cbca_iters(const sm_ctx* c) { return c->dw_on ? 2 : c->p.cbca_iterations; }
 // refine()'s calPKR / subpixelEnhancement are on: they read vm[0] after dispOptimize
 bool refine_reads_volume(const sm_ctx* c) { return c->p.do_refine && (c->rx_pkr || c->rx_se || c->da_on); }
 
+// sm_refine_outlier_config's arguments against the context's parameters: the offending argument, named, or null.
+// No stage behind the call reads a volume, so every optimiser is allowed ("so" included).
+const char* outlier_config_error(const sm_params& p, int classify, int disp_mis, int rv_combine, int interpolate_type) {
+    if (!p.do_refine) return "sm_refine_outlier_config: the context has do_refine = 0 (refine() never runs)";
+    if (classify != 0 && classify != 1) return "classify must be 0 or 1 (LRConsistencyCheck instead of LRConsistencyCheck_normal)";
+    if (rv_combine != 0 && rv_combine != 1) return "rv_combine must be 0 or 1 (RV_combine_BG instead of regionVote_my)";
+    if (disp_mis < -32767 || disp_mis > -1) return "disp_mis must be in [-32767, -1] (DISP_MIS)";
+    if (disp_mis == p.disp_occ) return "disp_mis must differ from disp_occ (the two classes share no label)";
+    if (interpolate_type < 0 || interpolate_type > 3) return "interpolate_type must be in [0, 3] (interpolateType)";
+    return nullptr;
+}
+
 // combine2Vm_4's predicate on the nine-term sum s of integer arm maxima is boxFilter's (float)(s * (1.0 / 9))
 // (double sums, one rounding) < thres.  The product and its rounding are non-decreasing in s, so for every
 // finite thres the predicate is `s < t` with t the first sum that fails it; the scan covers every sum the arm

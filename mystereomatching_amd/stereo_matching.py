@@ -67,6 +67,13 @@ class StereoMatching:
     Do_discontinuityAdjust = False
     DA_CANNY = _capi.REFINE_DA_DEFAULTS[:2]
     DA_BLUR_TAPS = _capi.REFINE_DA_DEFAULTS[2:]
+    # two source switches of refine() (sm_refine_outlier_config), as commented out in the shipped build:
+    # LRC_CLASSIFY = True runs LRConsistencyCheck (cpp:1367, 2284-2335: failed pixels become DISP_OCC / DISP_MIS and
+    # refine() leaves the mask in self.LRC_Err_Mask) instead of LRConsistencyCheck_normal; RV_COMBINE_BG = True runs
+    # RV_combine_BG (cpp:1408, 7146-7216: a float ratio, the filler chosen per class by Parameters.interpolateType)
+    # instead of regionVote_my
+    LRC_CLASSIFY = False
+    RV_COMBINE_BG = False
 
     class Parameters:
         """StereoMatching::Parameters (h:85-351): the fields the hot path reads."""
@@ -114,7 +121,9 @@ class StereoMatching:
             self.rows, self.cols = h, w
             self.LRmaxDiff = 0.0                       # h:212
             self.DISP_OCC = -2 * 16                    # h:216
+            self.DISP_MIS = -3 * 16                    # h:217
             self.DISP_PKR = -4 * 16                    # h:218
+            self.interpolateType = 0                   # h:178, 310: RV_combine_BG's filler (RV_COMBINE_BG)
             self.bgIplDepth = 1000                     # h:311
             self.region_vote_nums = 2                  # h:306
             self.rv_ratio, self.rv_s = 0.4, 20         # refine(): rv_ratio[] / rv_s[] (cpp:1400-1401)
@@ -229,6 +238,12 @@ class StereoMatching:
             st = self._lib.sm_refine_da_config(ctx, 1, int(self.DA_CANNY[0]), int(self.DA_CANNY[1]),
                                                int(self.DA_BLUR_TAPS[0]), int(self.DA_BLUR_TAPS[1]))
             _capi.check(self._lib, ctx, st, "sm_refine_da_config")
+        self.LRC_Err_Mask: Optional[np.ndarray] = None  # LRConsistencyCheck's mask (LRC_CLASSIFY)
+        self._outlier = (self._refine_on and bool(self.LRC_CLASSIFY), self._refine_on and bool(self.RV_COMBINE_BG))
+        if any(self._outlier):
+            st = self._lib.sm_refine_outlier_config(ctx, int(self._outlier[0]), int(param.DISP_MIS), int(self._outlier[1]),
+                                                    int(param.interpolateType))
+            _capi.check(self._lib, ctx, st, "sm_refine_outlier_config")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -269,6 +284,9 @@ class StereoMatching:
         if self._refine_ext[2]:
             self.SE = np.empty((self.h_, self.w_), np.float32)
             _capi.check(self._lib, self._ctx, self._lib.sm_get_subpixel(self._ctx, _capi.ptr(self.SE)), "SE")
+        if self._outlier[0]:
+            self.LRC_Err_Mask = np.empty((self.h_, self.w_), np.uint8)
+            _capi.check(self._lib, self._ctx, self._lib.sm_get_lrc_mask(self._ctx, _capi.ptr(self.LRC_Err_Mask)), "LRC_Err_Mask")
         if self._refine_da:
             self.DA_Edge = np.empty((self.h_, self.w_), np.uint8)
             _capi.check(self._lib, self._ctx, self._lib.sm_get_da_edges(self._ctx, _capi.ptr(self.DA_Edge)), "DA_Edge")
@@ -381,6 +399,9 @@ class StereoBatch:
         refine_ext = overrides.pop("refine_ext", None)
         # refine()'s discontinuity adjustment (sm_refine_da_config): refine_da is a dict of refine_da_config's arguments
         refine_da = overrides.pop("refine_da", None)
+        # refine()'s outlier classification (sm_refine_outlier_config): refine_outlier is a dict of
+        # refine_outlier_config's arguments
+        refine_outlier = overrides.pop("refine_outlier", None)
         # the cross-scale pyramid inside run() (sm_pyramid_config): py_lvl = PY_LEV of main_.cpp:131, applied last
         py_lvl = int(overrides.pop("py_lvl", 1))
         p = _capi.default_params(max_disp, rows, cols, **overrides)
@@ -404,6 +425,8 @@ class StereoBatch:
             self.refine_ext_config(**dict(refine_ext))
         if refine_da:
             self.refine_da_config(**dict(refine_da))
+        if refine_outlier:
+            self.refine_outlier_config(**dict(refine_outlier))
         if py_lvl != 1:
             self.pyramid_config(py_lvl)
         self.n = 0
@@ -624,6 +647,21 @@ class StereoBatch:
         """sm_get_da_edges: the first pair's edge map [H][W] (0 / 255) of the last run with the adjustment on."""
         out = np.empty(self.shape[:2], np.uint8)
         _capi.check(self._lib, self._ctx, self._lib.sm_get_da_edges(self._ctx, _capi.ptr(out)), "get_da_edges")
+        return out
+
+    def refine_outlier_config(self, classify: bool = False, disp_mis: int = _capi.REFINE_OUTLIER_DEFAULTS[0],
+                              rv_combine: bool = False, interpolate_type: int = _capi.REFINE_OUTLIER_DEFAULTS[1]):
+        """sm_refine_outlier_config: refine()'s classifying LR check (DISP_OCC / DISP_MIS labels and LRC_Err_Mask)
+        and RV_combine_BG in the region-vote rounds (both off by default), from the next run on; needs
+        do_refine = 1."""
+        st = self._lib.sm_refine_outlier_config(self._ctx, int(bool(classify)), int(disp_mis), int(bool(rv_combine)),
+                                                int(interpolate_type))
+        _capi.check(self._lib, self._ctx, st, "refine_outlier_config")
+
+    def get_lrc_mask(self) -> np.ndarray:
+        """sm_get_lrc_mask: the first pair's LRC_Err_Mask [H][W] (0 / 255) of the last run with classify on."""
+        out = np.empty(self.shape[:2], np.uint8)
+        _capi.check(self._lib, self._ctx, self._lib.sm_get_lrc_mask(self._ctx, _capi.ptr(out)), "get_lrc_mask")
         return out
 
     def get_pkr_mask(self) -> np.ndarray:

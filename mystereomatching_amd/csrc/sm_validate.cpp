@@ -186,7 +186,15 @@ sm_status validate(const sm_params& p, std::string& why) {
     }
     if (p.aggregation == SM_AGG_NL) {
         if (!(p.nl_sigma > 0)) return bad("nl_sigma must be > 0");
-        // ctmf's 3x3 median asserts width >= 3 and height >= 3 (NL/ctmf.c:211-212)
+        // ctmf's 3x3 median asserts width >= 3 and height >= 3 (NL/ctmf.c:211-212).  That is not its whole
+        // domain as mst() calls it (r = 1, memsize = rows * cols * 3, qx_mst_kruskals_image.cpp:174): the
+        // stripe count divides by memsize / sizeof(Histogram) - 2 r in unsigned arithmetic (ctmf.c:414,
+        // sizeof(Histogram) = 544), which is 0 for 363 <= rows * cols <= 543.  There the reference, built with
+        // assertions, aborts at ctmf.c:211 (measured with the reference's own code, tests/test_ref_nl.py); built
+        // without, it does not return.  Below 363 px the wrap-around yields one stripe and the filter works;
+        // from 544 px it works as designed.  Inside the window this library (and the oracle) return the plain
+        // clamped 3x3 median the reference gives everywhere else -- behaviour the reference does not have;
+        // the sizes stay accepted.
         if (p.rows < 3 || p.cols < 3) return bad("aggregation NL needs rows, cols >= 3 (ctmf median)");
         // the GPU tree walk indexes the batch's tour arcs (4 per pixel) with 32-bit ints
         if (4.0 * (double)p.rows * (double)p.cols * (double)(p.batch_capacity > 0 ? p.batch_capacity : 1) >= 2147483647.0)

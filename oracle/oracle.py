@@ -1,6 +1,8 @@
 """ctypes wrapper of the CPU restatement (oracle/sm_oracle.c) — TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED (see sm_oracle.h): the reference cannot be built here and ships no fixtures.
+PARITY UNPINNED (see sm_oracle.h): the reference cannot be built here and ships no fixtures --
+except NL's median, tree, table and filter, which tests/test_ref_nl.py holds to the reference's own
+NL/ code (oracle/ref_nl.mk, oracle/ref_nl.py).
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
 from __future__ import annotations

@@ -18,7 +18,8 @@ from mystereomatching_amd import synthetic as S
 pytestmark = pytest.mark.gpu
 
 GOLDEN = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
-                if not os.path.basename(p).startswith(("large_", "bench_maps_")))   # those: test_gpu_large_fixtures.py
+                if not os.path.basename(p).startswith(("large_", "bench_maps_",    # those: test_gpu_large_fixtures.py
+                                                       "ref_nl")))                 # that one: test_ref_nl.py
 
 
 def bits(a):

@@ -1,6 +1,7 @@
 """CPU: the oracle's GF (MY_GUIDE) and NL aggregators against the independent numpy restatement
-(tests/pyref_agg.py), bit for bit, plus structural checks of the NL tree.  PARITY UNPINNED (the
-reference needs OpenCV / ximgproc and ships no fixtures); see oracle/sm_oracle_agg.c."""
+(tests/pyref_agg.py), bit for bit, plus structural checks of the NL tree.  GF: PARITY UNPINNED (the
+reference needs OpenCV / ximgproc and ships no fixtures); see oracle/sm_oracle_agg.c.  NL is pinned
+to the reference's own NL/ code by tests/test_ref_nl.py."""
 import numpy as np
 import pytest
 

@@ -49,6 +49,9 @@
  *                         (LRConsistencyCheck cpp:2284-2335; RV_combine_BG cpp:7146-7216 with
  *                          cal_histogram_for_HV cpp:6830-6862, backgroundInterpolateCore cpp:6964-7043)
  *   sm_get_lrc_mask    <- member LRC_Err_Mask as LRConsistencyCheck leaves it (cpp:2291-2309)
+ *   sm_eval_config, sm_upload_truth, sm_get_stage_errors, sm_get_stage_maps <- saveFromDisp<short, 0> -> calErr
+ *                         after dispOptimize and the stages of refine() (cpp:588-601, 1102, 1131, 1373-1501;
+ *                         h:1748-1825), DT and I_mask (cpp:2072-2075)
  *   sm_get_volume / sm_set_volume <- public member vm[view]       stereoMatching.h:2720
  *   sm_get_arms        <- public member HVL[view]                    stereoMatching.h:2717
  *   sm_destroy         <- delete smPsy[p]                            main_.cpp:173-178
@@ -309,7 +312,7 @@ SM_API sm_status sm_run(sm_ctx* ctx, int32_t n, float reg_lambda, int16_t* disp_
  * sm_aws_config, sm_bf_config, sm_gfnl_config, sm_cbca_double_config (arm_l2 and arm_l_out2 divided by 2^s) and
  * sm_cbca_intersect_config apply to every level, whichever order they and this call come in; a level that cannot
  * take a setting fails that call with the level named and every level unchanged.  sm_vmtop_config,
- * sm_refine_ext_config, sm_refine_da_config and sm_refine_outlier_config concern level 0 only.  The staged calls keep their contracts
+ * sm_refine_ext_config, sm_refine_da_config, sm_refine_outlier_config and sm_eval_config concern level 0 only.  The staged calls keep their contracts
  * (sm_solve_all refuses py_lev != 1; sm_solve_all_pyr takes one context per level).
  * Checked before any device call: py_lvl outside [1, 8] and a level that sm_create would refuse (rows or cols < 2,
  * an aggregation's minimum size, ..) are SM_EINVAL with the level and its reason in sm_last_error.  On a live
@@ -555,6 +558,53 @@ SM_API sm_status sm_refine_outlier_config(sm_ctx* ctx, int32_t classify, int32_t
 /* Pair 0's LRC_Err_Mask (0 / 255) of the last sm_refine / sm_run with classify on: rows x cols bytes.  SM_ESTATE
  * before that; SM_EINVAL for a null dst.  Both are decided without a device. */
 SM_API sm_status sm_get_lrc_mask(sm_ctx* ctx, uint8_t* dst);
+
+/* The reference's error table (saveFromDisp -> calErr, cpp:588-601, h:1748-1825), per pair and per stage, built on the
+ * device inside sm_run / sm_disp_optimize / sm_refine.  Wherever the reference calls saveFromDisp<short, 0> -- after
+ * dispOptimize and after the stages of refine() -- one launch ("eval_stage") reads the left map of every pair of the
+ * group while it is still in cache, against the uploaded ground truth and region masks, and leaves one record per
+ * (pair, stage, region); a second launch ("eval_final") sums the blocks' partial records.  Regions in I_mask's order:
+ * nonocc, all, disc. */
+typedef struct sm_stage_err {      /* one (pair, stage, region); 32 bytes */
+    uint32_t count;                /* pixels with mask == 255 (calErr's sumNum) */
+    uint32_t invalid;              /* of those, DP < 0 */
+    uint32_t bad[4];               /* of those, DP < 0 or |DT - DP| > thres[k] (errorNumer); k >= nthres: 0 */
+    double   sum_sq;               /* sum of dif^2 over valid pixels + 2 per invalid pixel (errorValueSum's terms) */
+} sm_stage_err;
+/* Not sm_params fields (the struct keeps its size): off by default; with it off nothing is launched or allocated.
+ * on, keep_maps in {0, 1}; nthres in [1, 4] thresholds, each >= +0 and finite (calErr's `dif > THRES`).  keep_maps
+ * also keeps every stage's maps (the same launch stores them).  The truth planes, the partial records, the table and
+ * the snapshots are allocated on the enabling call (batch_capacity pairs, 7 + region_vote_nums stages at the most).
+ * Stage list, from the settings as they are when the run starts, under the reference's names:
+ *   "so" | "vmTop" (sm_vmtop_config on, optimiser not "so") | "wta" ("sgm" and ""): DP[0] as dispOptimize left it;
+ *   with do_refine: "od" (after the LR check, either form), "PKR" (do_pkr), "RV0" .. "RV{k-1}" (do_region_vote,
+ *   k = region_vote_nums), "pi" (do_proper_ipol, once after the last round), "BG" (do_bg_ipol, also at depth 0),
+ *   "da" (the discontinuity adjustment), "mb" (do_last_median_blur).
+ * The reference's "se" and the "mb" after it read the int16 map as floats (cpp:1487, 1492): undefined, left out.
+ * sm_run records every stage; sm_disp_optimize records stage 0 and sm_refine the rest.  With sm_pyramid_config the
+ * table is level 0's.  sum_sq is a double sum in a fixed order that sm_eval_stage_host restates: the table
+ * is bit-identical from run to run and for every sub_batch / num_streams.  PBM = (float)bad[k] / count and
+ * RMS = sqrtf((float)sum_sq / count), both 0 for count == 0 (as sm_cal_err; sm_cal_err stays the reference's float
+ * accumulation in raster order).  SM_EINVAL with the argument named in sm_last_error; the arguments are checked
+ * without a device.  SM_ESTATE on a pyramid level context. */
+SM_API sm_status sm_eval_config(sm_ctx* ctx, int32_t on, int32_t keep_maps, int32_t nthres, const float* thres);
+/* Ground truth DT ([n][H][W] floats) and the region masks ([n][H][W] bytes each) of the first n pairs, host
+ * pointers; a NULL mask is an absent region (count 0: the reference's `continue`).  The masks are packed into one
+ * byte per pixel, bit r set where mask_r == 255.  Synchronous, ordered like sm_upload_batch; the truth stays until
+ * the next call.  A run of n pairs with evaluation on and fewer than n truth planes returns SM_ESTATE. */
+SM_API sm_status sm_upload_truth(sm_ctx* ctx, int32_t n, const float* gt, const uint8_t* nonocc, const uint8_t* all,
+                                 const uint8_t* disc);
+/* The stages of the last run (before any run: what the next sm_run would record); NULL for a stage out of range. */
+SM_API int32_t sm_eval_stage_count(const sm_ctx* ctx);
+SM_API const char* sm_eval_stage_name(const sm_ctx* ctx, int32_t stage);
+/* The table of the first n pairs of the last run, [n][stages][3], and (keep_maps) one stage's maps, [n][H][W]; both
+ * synchronise like sm_download_disp.  SM_ESTATE before any run with evaluation on. */
+SM_API sm_status sm_get_stage_errors(sm_ctx* ctx, int32_t n, sm_stage_err* out);
+SM_API sm_status sm_get_stage_maps(sm_ctx* ctx, int32_t n, int32_t stage, int16_t* out);
+/* The device's arithmetic on the host, in the same order, for one rows x cols map: `region` is the packed byte
+ * plane (bit r = region r).  Defines sum_sq bit for bit; needs no device. */
+SM_API void sm_eval_stage_host(const int16_t* disp, const float* gt, const uint8_t* region, int32_t rows, int32_t cols,
+                               int32_t nthres, const float* thres, sm_stage_err out[3]);
 
 /* Diagnostics used by the parity tests. */
 /* CBCA's double window: pair 0's arm_Mask of the last sm_cost_calculate / sm_run, rows x cols bytes (1 where

@@ -353,6 +353,9 @@ class StereoMatching {
     // float ratio, the filler chosen per class by Parameters::interpolateType) instead of regionVote_my
     inline static bool LRC_CLASSIFY = false;
     inline static bool RV_COMBINE_BG = false;
+    // the reference's err txt (saveFromDisp -> calErr after dispOptimize and after refine()'s stages; sm_eval_config):
+    // with DT given, the table is built on the GPU while dispOptimize and refine() run; stageErrors() returns its rows
+    inline static bool Do_stageErrors = false;
     inline static bool Do_properIpol = true;       // h:76
     inline static bool Do_lastMedianBlur = true;   // h:80
     // `#define MY_GUIDE` (h:38, commented out in the shipped build) as a switch: false = GF runs
@@ -522,6 +525,48 @@ class StereoMatching {
     }
     std::vector<RegionErr> calErr() { return calErr<int16_t>(DP[0], DT, "DP0"); }
 
+    // The err-txt rows of the last dispOptimize (+ refine): one per stage at which the reference calls
+    // saveFromDisp<short, 0> and per region whose mask was given, from the table the GPU built (sm_get_stage_errors),
+    // with PBM = (float)bad / count and RMS = sqrtf((float)sum_sq / count), 0 for an empty region.
+    struct StageErr {
+        std::string procedure, region;
+        float PBM, RMS;
+    };
+    std::vector<StageErr> stageErrors() {
+        if (!eval_on_) throw std::logic_error("stageErrors needs StereoMatching::Do_stageErrors = true and DT at construction");
+        static const char* names[3] = {"nonocc", "all", "disc"};
+        const int S = sm_eval_stage_count(ctx_);
+        std::vector<sm_stage_err> t((size_t)std::max(S, 1) * 3);
+        check(sm_get_stage_errors(ctx_, 1, t.data()), "stageErrors");
+        std::vector<StageErr> out;
+        for (int s = 0; s < S; s++)
+            for (int region = 0; region < 3; region++) {
+                if (I_mask[region].empty()) continue;
+                const sm_stage_err& e = t[(size_t)s * 3 + region];
+                StageErr r{sm_eval_stage_name(ctx_, s), names[region], 0.f, 0.f};
+                if (e.count) {
+                    r.PBM = (float)e.bad[0] / e.count;
+                    r.RMS = sqrtf((float)e.sum_sq / e.count);
+                }
+                out.push_back(r);
+            }
+        return out;
+    }
+    // the rows as calErr writes them to the err txt (h:1756, 1799, 1817): one line per stage
+    std::string stageErrorsText() {
+        std::ostringstream o;
+        std::string last;
+        bool first = true;
+        for (const StageErr& r : stageErrors()) {
+            if (first || r.procedure != last) o << (first ? "" : "\n") << r.procedure << "\t";
+            o << r.region << "\tPBM: " << r.PBM << "\tRMS: " << r.RMS << "\t";
+            last = r.procedure;
+            first = false;
+        }
+        if (!first) o << "\n";
+        return o.str();
+    }
+
     Mat DP[2];        // int16 H x W disparity, -1 = invalid (h:2724)
     Mat DT;           // ground truth (cpp:2072)
     Mat SE;           // float H x W: refine()'s local SE after its median (cpp:1484-1490), with Do_subpixelEnhancement
@@ -535,7 +580,7 @@ class StereoMatching {
 
    private:
     bool refine_on_ = false, csv_open_ = false;
-    bool pkr_on_ = false, se_on_ = false, da_on_ = false, lrc_on_ = false;
+    bool pkr_on_ = false, se_on_ = false, da_on_ = false, lrc_on_ = false, eval_on_ = false;
     std::ostringstream csv_;
     std::vector<std::string> times_;
 
@@ -638,6 +683,19 @@ class StereoMatching {
             check(sm_refine_outlier_config(ctx_, LRC_CLASSIFY ? 1 : 0, param.DISP_MIS, RV_COMBINE_BG ? 1 : 0, param.interpolateType),
                   "sm_refine_outlier_config");
             lrc_on_ = LRC_CLASSIFY;
+        }
+        if (Do_stageErrors && !DT.empty()) {
+            if (DT.depth() != CV_32F || DT.rows != h_ || DT.cols != w_) throw std::invalid_argument("Do_stageErrors: DT must be CV_32F H x W");
+            const float th = (float)param.errorThreshold;
+            check(sm_eval_config(ctx_, 1, 0, 1, &th), "sm_eval_config");
+            const std::vector<float> dt = DT.packed<float>();
+            std::vector<uint8_t> m[3];
+            for (int r = 0; r < 3; r++)
+                if (!I_mask[r].empty()) m[r] = I_mask[r].packed<uint8_t>();
+            check(sm_upload_truth(ctx_, 1, dt.data(), m[0].empty() ? nullptr : m[0].data(), m[1].empty() ? nullptr : m[1].data(),
+                                  m[2].empty() ? nullptr : m[2].data()),
+                  "sm_upload_truth");
+            eval_on_ = true;
         }
         check(sm_set_images(ctx_, I1_c.data, I2_c.data, I1_c.step, I1_g.data, I2_g.data, I1_g.step), "sm_set_images");
     }

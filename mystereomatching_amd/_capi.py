@@ -64,6 +64,18 @@ class sm_params(C.Structure):
     ]
 
 
+class sm_stage_err(C.Structure):
+    """Mirror of struct sm_stage_err (include/sm_capi.h): one (pair, stage, region) of the error table."""
+
+    _fields_ = [("count", C.c_uint32), ("invalid", C.c_uint32), ("bad", C.c_uint32 * 4), ("sum_sq", C.c_double)]
+
+
+# the same record as a numpy dtype (StereoBatch.stage_errors)
+STAGE_ERR_DTYPE = [("count", "<u4"), ("invalid", "<u4"), ("bad", "<u4", (4,)), ("sum_sq", "<f8")]
+EVAL_REGIONS = ("nonocc", "all", "disc")   # I_mask's order (cpp:2073-2075)
+EVAL_MAX_THRES = 4
+
+
 # Every SM_API symbol declared in include/sm_capi.h: (name, restype, argtypes).
 _P = C.c_void_p
 _u8p = C.POINTER(C.c_uint8)
@@ -134,6 +146,13 @@ SIGNATURES = [
     ("sm_set_da_edges", C.c_int, [_P, _P]),
     ("sm_refine_outlier_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("sm_get_lrc_mask", C.c_int, [_P, _P]),
+    ("sm_eval_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
+    ("sm_upload_truth", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
+    ("sm_eval_stage_count", C.c_int32, [_P]),
+    ("sm_eval_stage_name", C.c_char_p, [_P, C.c_int32]),
+    ("sm_get_stage_errors", C.c_int, [_P, C.c_int32, _P]),
+    ("sm_get_stage_maps", C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    ("sm_eval_stage_host", None, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),
 ]
 
 _lib = None

@@ -492,6 +492,7 @@ sm_status sm_disp_optimize(sm_ctx* c, int16_t* disp_out) {
     if (s) return s;
     if (c->stage < 2 || c->stage > 3) return fail(c, SM_ESTATE, "sm_disp_optimize must follow sm_cost_calculate / sm_solve_all");
     if ((s = wait_copy(c))) return s;
+    if ((s = eval_begin(c, c->n_loaded, true, false))) return s;
     for (int v = 0; v < opt_views(c->p); v++)   // num (cpp:1054, 1093, 1110)
         if ((s = run_optimize(c, v, at(c, 0, c->n_loaded, c->st)))) return s;
     c->stage = 4;
@@ -508,6 +509,7 @@ sm_status sm_refine(sm_ctx* c, int16_t* disp_out) {
     if (refine_reads_volume(c) && c->p.optimization == SM_OPT_SGM && !c->p.keep_final_volume && !c->vt_on && !c->rx_vol_ok)
         return fail(c, SM_ESTATE, "sm_refine: do_pkr / do_subpixel / the discontinuity adjustment were switched on after sm_disp_optimize (SGM kept no path sum)");
     if ((s = wait_copy(c))) return s;
+    if ((s = eval_begin(c, c->n_loaded, false, true))) return s;
     if ((s = run_refine(c, at(c, 0, c->n_loaded, c->st)))) return s;
     c->stage = 5;
     if (disp_out) return sm_download_disp(c, 1, disp_out);

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "sm_eval_core.h"
 #include "sm_kernels.h"
 
 struct ProfRec {
@@ -150,6 +151,24 @@ struct sm_ctx {
     int16_t* oc_cand = nullptr;    // [cap][npix] the classified holes' results of a round (types 2, 3)
     int16_t* oc_rowlast = nullptr; // [cap][rows] each row's last classified result
     bool oc_ran = false;           // the last refine filled the mask
+    // the per-stage error table (sm_eval_config; sm_eval.hip, sm_eval_host.cpp): the settings, the uploaded truth,
+    // the blocks' partial records, the table and (keep_maps) the stages' snapshots.  ev_smax = 7 + region_vote_nums
+    // stages is the most a run can record, so the buffers never move once evaluation is on
+    bool ev_on = false, ev_keep = false;
+    sm::EvalThres ev_th{{1.0f, 0.f, 0.f, 0.f}, 1};
+    float* ev_gt = nullptr;            // [cap][npix] DT
+    uint8_t* ev_reg = nullptr;         // [cap][npix] bit r: I_mask[r] == 255
+    sm_stage_err* ev_part = nullptr;   // [cap][ev_smax][3][ev_nblk]
+    sm_stage_err* ev_table = nullptr;  // [cap][ev_smax][3]
+    int16_t* ev_snap = nullptr;        // [ev_smax][ev_snap_stride]: [cap][npix] per stage
+    size_t ev_snap_stride = 0;         // cap * npix rounded up to 8 elements (a stage keeps pair 0's alignment)
+    size_t ev_nblk = 0;                // blocks per pair
+    int ev_smax = 0;
+    int ev_truth_n = 0;                // truth planes loaded (sm_upload_truth)
+    std::vector<std::string> ev_names; // the stages the last run recorded
+    std::vector<std::string> ev_preview;   // before any run: what the next sm_run would record (sm_eval_stage_name)
+    int ev_n = 0;                      // the pairs it recorded
+    bool ev_kept = false;              // it kept its maps
     // aggregation "NL" (and "GFNL"): median image, edge weights, spanning trees, the tree walk, filter values
     uint8_t* nl_med = nullptr;  // [cap][npix][3]
     uint8_t* nl_ew = nullptr;   // [cap][ne]
@@ -474,6 +493,12 @@ sm_status run_scale(sm_ctx* c, int view, float w, const Group& G);
 sm_status run_optimize(sm_ctx* c, int view, const Group& G);
 sm_status run_refine(sm_ctx* c, const Group& G);
 sm_status run_da_image(sm_ctx* c, const Group& G, int first, const int16_t* dp);
+
+// sm_eval_host.cpp: the error table's stage list and its launches on the group's stream
+std::vector<std::string> eval_stage_names(const sm_ctx* c, bool stage0, bool refine);
+sm_status eval_begin(sm_ctx* c, int n, bool stage0, bool refine);   // a run starts: checks the truth, fixes the list
+sm_status run_eval_stage(sm_ctx* c, const Group& G, int stage, const int16_t* map);
+sm_status run_eval_final(sm_ctx* c, const Group& G, int stage0, int nstages);
 
 // sm_stages_agg.cpp
 sm_status nl_open(sm_ctx* c, hipStream_t st);

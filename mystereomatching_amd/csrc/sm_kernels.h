@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/sm_capi.h"
+
 namespace sm {
 
 enum { SM_M_CENSUS_GRAD = 0, SM_M_CENSUS = 1, SM_M_AD_CENSUS = 2, SM_M_AD = 3 };
@@ -451,5 +453,13 @@ void launch_lr_classify(int16_t* d0, const int16_t* d1, uint8_t* mask, int n, in
                         int disp_occ, int disp_mis, hipStream_t st);
 void launch_rv_combine(const RvcArgs& a, hipStream_t st);          // D <= 1024 (sm_params' limit): 17 KiB of LDS
 void launch_rv_carry(const RvcArgs& a, hipStream_t st);            // types 2, 3, after launch_rv_combine
+
+// ---- the per-stage error table (sm_eval_config; sm_eval.hip, arithmetic and EvalArgs in sm_eval_core.h) ----
+struct EvalArgs;
+// one stage's maps of n pairs against the truth: partial records per (pair, stage, region, block)
+void launch_eval_stage(const EvalArgs& a, int n, hipStream_t st);
+// the partials of stages [stage0, stage0 + nstages) of n pairs summed into table[pair][stages_alloc][3]
+void launch_eval_final(const sm_stage_err* part, sm_stage_err* table, size_t nblk, int stages_alloc, int stage0, int nstages,
+                       int n, hipStream_t st);
 
 }  // namespace sm

@@ -225,6 +225,7 @@ sm_status sm_run(sm_ctx* c, int32_t n, float reg_lambda, int16_t* disp_out) {
         c->place_trials = 0;
         if ((s = join_all(c)) || (s = place_volumes(c, k, n, reg_lambda))) return s;
     }
+    if ((s = eval_begin(c, n, true, c->p.do_refine != 0))) return s;   // (the error table: truth loaded, stage list fixed)
     const float m = 1 + reg_lambda;
     // Sub-batches: all stages of a group of pairs run back to back so that one pass's output is
     // still in the 256 MB Infinity Cache when the next pass reads it.  With SM_STREAMS = s > 1 the

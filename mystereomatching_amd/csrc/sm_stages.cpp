@@ -456,7 +456,14 @@ sm_status run_optimize(sm_ctx* c, int view, const Group& G) {
                             [&] { sm::launch_wta(vm, disp, G.n, p.rows, p.cols, p.num_disparities, G.st); });
         if (s) return s;
     }
-    if (vmtop) return run_vmtop(c, view, G, vm, disp);
+    if (vmtop) {
+        sm_status s = run_vmtop(c, view, G, vm, disp);
+        if (s) return s;
+    }
+    if (c->ev_on && view == 0) {   // saveFromDisp<short, 0>(DP[0], "so" | name) (cpp:1102, 1131): the table's stage 0
+        sm_status s = run_eval_stage(c, G, 0, disp);
+        return s ? s : run_eval_final(c, G, 0, 1);
+    }
     return SM_OK;
 }
 
@@ -504,6 +511,10 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
     const double map = (double)G.n * c->npix * 2;
     const double np = (double)G.n * c->npix;
     sm_status s;
+    // the error table (sm_eval_config): one entry wherever the reference calls saveFromDisp<short, 0> on DP[0],
+    // in eval_stage_names' order; stage 0 is run_optimize's
+    int es = 1;
+    auto saved = [&](const int16_t* m) { return c->ev_on ? run_eval_stage(c, G, es++, m) : SM_OK; };
     if (c->oc_classify) {   // LRConsistencyCheck (cpp:2284-2335) in place of LRConsistencyCheck_normal (cpp:1364-1367)
         uint8_t* mask = G.slice(c->oc_mask, c->npix);
         // reads DP[0] and DP[1], writes the labels and the mask
@@ -516,7 +527,7 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
         s = timed(c, G.st, "refine_lr_check", 3 * map,
                   [&] { sm::launch_lr_check(G.disp, G.disp1, G.n, H, W, p.lr_max_diff, G.st); });
     }
-    if (s) return s;
+    if (s || (s = saved(G.disp))) return s;   // "od" (cpp:1373)
     if (c->rx_pkr) {   // calPKR + signDp_UsingPKR (cpp:1378-1383) on vm[0] as dispOptimize left it
         sm::PkrArgs a{};
         a.vm = G.vm0;
@@ -530,6 +541,7 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
         a.disp_pkr = c->rx_disp_pkr;
         if ((s = timed(c, G.st, "refine_pkr", (double)G.n * c->nvol * 4.0 + np * 5, [&] { sm::launch_pkr(a, G.st); }))) return s;
         c->rx_pkr_ran = true;
+        if ((s = saved(G.disp))) return s;   // "PKR" (cpp:1382)
     }
     int16_t* cur = G.disp;
     int16_t* nxt = G.disp_tmp;
@@ -565,14 +577,17 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
                 return s;
             }
             std::swap(cur, nxt);
+            if ((s = saved(cur))) return s;   // "RV<i>" (cpp:1420)
         }
-    if (p.do_proper_ipol)
+    if (p.do_proper_ipol) {
         for (int i = 0; i < p.region_vote_nums; i++) {
             if ((s = timed(c, G.st, "refine_proper_ipol", 2 * map,
                            [&] { sm::launch_proper_ipol(cur, nxt, G.px, G.n, H, W, p.disp_occ, G.st); })))
                 return s;
             std::swap(cur, nxt);
         }
+        if ((s = saved(cur))) return s;   // "pi", once (cpp:1448)
+    }
     if (c->rx_bg && c->rx_depth > 0) {   // BGIpol (cpp:1454-1465); a depth of 0 searches nothing
         sm::BgArgs a{};
         a.src = cur;
@@ -585,6 +600,7 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
         if ((s = timed(c, G.st, "refine_bg_ipol", 4 * map, [&] { sm::launch_bg_ipol(a, G.st); }))) return s;
         std::swap(cur, nxt);
     }
+    if (c->rx_bg && (s = saved(cur))) return s;   // "BG" (cpp:1459), also where depth 0 skipped the kernel
     if (c->da_on) {   // discontinuityAdjust(DP[0]) (cpp:1473-1476) on vm[0] as dispOptimize left it
         const sm::DaArgs a = da_args(c, G);
         if (c->da_user_on) {   // sm_set_da_edges: the supplied map for every pair
@@ -602,6 +618,7 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
             return s;
         std::swap(cur, nxt);
         c->da_ran = true;
+        if ((s = saved(cur))) return s;   // "da" (cpp:1477)
     }
     if (c->rx_se) {   // subpixelEnhancement + medianBlur(SE, SE, 3) (cpp:1482-1495); DP[0] stays
         float* raw = G.slice(c->se_tmp, c->npix);
@@ -617,7 +634,9 @@ sm_status run_refine(sm_ctx* c, const Group& G) {
     if (p.do_last_median_blur) {
         if ((s = timed(c, G.st, "refine_median3", 2 * map, [&] { sm::launch_median3(cur, nxt, G.n, H, W, G.st); }))) return s;
         std::swap(cur, nxt);
+        if ((s = saved(cur))) return s;   // "mb" (cpp:1501)
     }
+    if (c->ev_on && (s = run_eval_final(c, G, 1, es - 1))) return s;
     if (cur != G.disp) HIP_TRY(c, hipMemcpyAsync(G.disp, cur, (size_t)map, hipMemcpyDeviceToDevice, G.st));
     return SM_OK;
 }

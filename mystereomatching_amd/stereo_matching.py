@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _capi
-from .evaluate import cal_err
+from .evaluate import cal_err, err_rows, stage_errors_array
 
 
 class StereoMatching:
@@ -74,6 +74,10 @@ class StereoMatching:
     # instead of regionVote_my
     LRC_CLASSIFY = False
     RV_COMBINE_BG = False
+    # the reference's err txt (saveFromDisp -> calErr after dispOptimize and after refine()'s stages; sm_eval_config):
+    # True (with DT given) builds the table on the GPU while dispOptimize and refine() run; stageErrors() returns
+    # its rows.  Read when an object is constructed, like the switches above
+    Do_stageErrors = False
 
     class Parameters:
         """StereoMatching::Parameters (h:85-351): the fields the hot path reads."""
@@ -244,6 +248,16 @@ class StereoMatching:
             st = self._lib.sm_refine_outlier_config(ctx, int(self._outlier[0]), int(param.DISP_MIS), int(self._outlier[1]),
                                                     int(param.interpolateType))
             _capi.check(self._lib, ctx, st, "sm_refine_outlier_config")
+        self._stage_errors = bool(self.Do_stageErrors) and DT is not None
+        if self._stage_errors:
+            th = (C.c_float * 1)(float(param.errorThreshold))
+            _capi.check(self._lib, ctx, self._lib.sm_eval_config(ctx, 1, 0, 1, th), "sm_eval_config")
+            gt = np.ascontiguousarray(DT, np.float32)
+            masks = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in self.I_mask]
+            if gt.shape != (h, w) or any(m is not None and m.shape != (h, w) for m in masks):
+                raise ValueError("DT and the masks must be HxW")
+            st = self._lib.sm_upload_truth(ctx, 1, _capi.ptr(gt), *[None if m is None else _capi.ptr(m) for m in masks])
+            _capi.check(self._lib, ctx, st, "sm_upload_truth")
         st = self._lib.sm_set_images(ctx, _capi.ptr(I1_c), _capi.ptr(I2_c), w * 3,
                                      _capi.ptr(I1_g), _capi.ptr(I2_g), w)
         _capi.check(self._lib, ctx, st, "sm_set_images")
@@ -334,6 +348,24 @@ class StereoMatching:
                 res[name] = cal_err(DP, self.DT, m, t)
         return res
 
+    def stageErrors(self):
+        """The err-txt rows of the last dispOptimize (+ refine): [(procedure, region, PBM, RMS)], one per stage at
+        which the reference calls saveFromDisp<short, 0> and per region whose mask was given, against DT with
+        errorThreshold (calErr, h:1748-1825).  Needs Do_stageErrors = True and DT when the object was constructed."""
+        if not self._stage_errors:
+            raise _capi.SMError(_capi.SM_ESTATE, "stageErrors needs StereoMatching.Do_stageErrors = True and DT at construction")
+        return err_rows(_stage_table(self._lib, self._ctx, 1)[0], [m is not None for m in self.I_mask])
+
+    stage_errors = stageErrors
+
+
+def _stage_table(lib, ctx, n: int):
+    """sm_get_stage_errors as a StageErrors array [n][stages][3] with the stages' names."""
+    S = int(lib.sm_eval_stage_count(ctx))
+    raw = np.zeros((n, max(S, 1), 3), _capi.STAGE_ERR_DTYPE)
+    _capi.check(lib, ctx, lib.sm_get_stage_errors(ctx, n, _capi.ptr(raw)), "stage_errors")
+    return stage_errors_array(raw, [lib.sm_eval_stage_name(ctx, i).decode() for i in range(S)])
+
 
 def SolveAll(smPyr: Sequence[StereoMatching], PY_LVL: int, REG_LAMBDA: float):
     """SolveAll (cpp:2142-2208).  PY_LVL = 1 (main_.cpp:131) scales vm; PY_LVL in [2, 8] combines
@@ -402,6 +434,8 @@ class StereoBatch:
         # refine()'s outlier classification (sm_refine_outlier_config): refine_outlier is a dict of
         # refine_outlier_config's arguments
         refine_outlier = overrides.pop("refine_outlier", None)
+        # the per-stage error table (sm_eval_config): eval is a dict of eval_config's arguments
+        eval_cfg = overrides.pop("eval", None)
         # the cross-scale pyramid inside run() (sm_pyramid_config): py_lvl = PY_LEV of main_.cpp:131, applied last
         py_lvl = int(overrides.pop("py_lvl", 1))
         p = _capi.default_params(max_disp, rows, cols, **overrides)
@@ -429,6 +463,8 @@ class StereoBatch:
             self.refine_outlier_config(**dict(refine_outlier))
         if py_lvl != 1:
             self.pyramid_config(py_lvl)
+        if eval_cfg:
+            self.eval_config(**dict(eval_cfg))
         self.n = 0
         self._async_out = []   # buffers of download_async copies still in flight
 
@@ -662,6 +698,41 @@ class StereoBatch:
         """sm_get_lrc_mask: the first pair's LRC_Err_Mask [H][W] (0 / 255) of the last run with classify on."""
         out = np.empty(self.shape[:2], np.uint8)
         _capi.check(self._lib, self._ctx, self._lib.sm_get_lrc_mask(self._ctx, _capi.ptr(out)), "get_lrc_mask")
+        return out
+
+    def eval_config(self, on: bool = True, keep_maps: bool = False, thresholds=(1.0,)):
+        """sm_eval_config: the reference's error table (calErr over nonocc / all / disc at every stage where it calls
+        saveFromDisp) built on the GPU inside run(), against upload_truth's data; up to four thresholds; keep_maps
+        also keeps every stage's maps (stage_maps).  Off by default."""
+        th = (C.c_float * max(len(thresholds), 1))(*[float(t) for t in thresholds])
+        st = self._lib.sm_eval_config(self._ctx, int(bool(on)), int(bool(keep_maps)), len(thresholds), th)
+        _capi.check(self._lib, self._ctx, st, "eval_config")
+
+    def upload_truth(self, gt, nonocc=None, all=None, disc=None):
+        """sm_upload_truth: ground truth [n][H][W] float32 and the region masks [n][H][W] uint8 (255 = inside;
+        None = region absent) of the uploaded pairs; stays until the next call."""
+        g = np.ascontiguousarray(_to_numpy(gt), np.float32)
+        if g.ndim != 3 or g.shape[1:] != self.shape[:2]:
+            raise ValueError("upload_truth: gt must be [n][H][W]")
+        ms = [None if m is None else np.ascontiguousarray(_to_numpy(m), np.uint8) for m in (nonocc, all, disc)]
+        if any(m is not None and m.shape != g.shape for m in ms):
+            raise ValueError("upload_truth: every mask must have gt's shape")
+        st = self._lib.sm_upload_truth(self._ctx, g.shape[0], _capi.ptr(g), *[None if m is None else _capi.ptr(m) for m in ms])
+        _capi.check(self._lib, self._ctx, st, "upload_truth")
+
+    def stage_names(self):
+        """The stages of the last run's table (before any run: what the next run would record)."""
+        return [self._lib.sm_eval_stage_name(self._ctx, i).decode() for i in range(self._lib.sm_eval_stage_count(self._ctx))]
+
+    def stage_errors(self):
+        """sm_get_stage_errors: the last run's table, a structured array [n][stages][3] (count, invalid, bad[4],
+        sum_sq) with .names, .pbm(k) and .rms()."""
+        return _stage_table(self._lib, self._ctx, self.n)
+
+    def stage_maps(self, stage: int) -> np.ndarray:
+        """sm_get_stage_maps: the n maps [n][H][W] as they were at `stage` (eval_config with keep_maps)."""
+        out = np.empty((self.n, self.shape[0], self.shape[1]), np.int16)
+        _capi.check(self._lib, self._ctx, self._lib.sm_get_stage_maps(self._ctx, self.n, int(stage), _capi.ptr(out)), "stage_maps")
         return out
 
     def get_pkr_mask(self) -> np.ndarray:

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Evaluate the GPU pipeline on a Middlebury-layout dataset, the way main_.cpp does (main:26-178).
 
-usage: tools/sm_eval.py ROOT [--objects teddy cones ...] [--refine] [--pyr L] [--device N]
+usage: tools/sm_eval.py ROOT [--objects teddy cones ...] [--refine] [--pyr L] [--device N] [--stages]
 
 For each object: load (mystereomatching_amd.dataset), Parameters(maxdisp, ...), costCalculate per
 pyramid level, SolveAll(PY_LEV, 0.3), dispOptimize [, refine], then calErr over nonocc / all /
 disc at t = 1 (errorThreshold, h:225) and t = 2 (BASELINE's bad-2.0).  Prints one JSON line per
-object.  No dataset ships with this repository; point ROOT at a local Middlebury copy.
+object.  --stages also prints the reference's err-txt lines (calErr after dispOptimize and after every stage of
+refine(), h:1756-1817), one per stage, from the table the GPU builds while the pipeline runs (sm_eval_config).
+No dataset ships with this repository; point ROOT at a local Middlebury copy.
 """
 import argparse
 import json
@@ -17,20 +19,28 @@ import time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 from mystereomatching_amd import SolveAll, StereoMatching, dataset, pyrDown  # noqa: E402
-from mystereomatching_amd.evaluate import cal_err_regions  # noqa: E402
+from mystereomatching_amd.evaluate import cal_err_regions, format_err_lines  # noqa: E402
 
 
 def run(sample, refine, levels, device):
+    return run_stages(sample, refine, levels, device, False)[:2]
+
+
+def run_stages(sample, refine, levels, device, stages=True):
+    """run() plus, with `stages`, calErr's err-txt lines of level 0 (one per stage)."""
     StereoMatching.costcalculation, StereoMatching.aggregation, StereoMatching.optimization = "censusGrad", "CBCA", "sgm"
     StereoMatching.Do_refine = refine
+    StereoMatching.Do_stageErrors = bool(stages) and sample.gt is not None
+    masks = sample.masks if stages else {}
     imgs = sample.pair()
     sms, md, sc = [], sample.max_disp, 1
     t0 = time.perf_counter()
     for _ in range(levels):
         H, W = imgs["lgray"].shape
         prm = StereoMatching.Parameters(md, H, W, 13, 1, 2, 109, 10, "", sc)
-        sm = StereoMatching(imgs["lbgr"], imgs["rbgr"], imgs["lgray"], imgs["rgray"], sample.gt, None, None, None,
-                            prm, device=device)
+        sm = StereoMatching(imgs["lbgr"], imgs["rbgr"], imgs["lgray"], imgs["rgray"], sample.gt if not (stages and sms) else None,
+                            masks.get("all") if not sms else None, masks.get("nonocc") if not sms else None,
+                            masks.get("disc") if not sms else None, prm, device=device)
         sm.costCalculate()
         sms.append(sm)
         md, sc = md // 2 + 1, sc * 2
@@ -39,7 +49,9 @@ def run(sample, refine, levels, device):
     dp = sms[0].dispOptimize()
     if refine:
         dp = sms[0].refine()
-    return dp, time.perf_counter() - t0
+    t = time.perf_counter() - t0
+    lines = format_err_lines(sms[0].stageErrors()) if StereoMatching.Do_stageErrors else []
+    return dp, t, lines
 
 
 def main():
@@ -50,10 +62,11 @@ def main():
     ap.add_argument("--pyr", type=int, default=1)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dataset", default="MD")
+    ap.add_argument("--stages", action="store_true", help="print calErr's err-txt line of every stage")
     a = ap.parse_args()
     for obj in a.objects:
         s = dataset.load(a.root, obj, a.dataset)
-        dp, t = run(s, a.refine, a.pyr, a.device)
+        dp, t, lines = run_stages(s, a.refine, a.pyr, a.device, a.stages)
         out = {"object": obj, "H": s.lgray.shape[0], "W": s.lgray.shape[1], "D": s.max_disp + 1,
                "refine": a.refine, "py_lev": a.pyr, "seconds": round(t, 4)}
         if s.gt is not None:
@@ -63,6 +76,8 @@ def main():
                     if t_ == 1.0:
                         out[f"rms_{r}"] = round(rms, 4)
         print(json.dumps(out))
+        for line in lines:
+            print(line)
 
 
 if __name__ == "__main__":

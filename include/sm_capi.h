@@ -26,6 +26,8 @@
  *   sm_disp_optimize   <- StereoMatching::dispOptimize + DP[0]       stereoMatching.cpp:1046-1136, h:2724
  *   sm_refine          <- StereoMatching::refine (Do_refine)         stereoMatching.cpp:1138-1511, main_.cpp:165-166
  *   sm_get_disp / sm_set_disp <- public member DP[view]              stereoMatching.h:2724
+ *   sm_so_config       <- the call commented in at dispOptimize's "so" branch (cpp:1096-1100):
+ *                         so cpp:6272-6394, so_R2L cpp:6683-6826, so_T2D cpp:6580-6681, and their Pn2 / Pn3 literals
  *   sm_vmtop_config    <- Parameters::Do_vmTop, vmTop_* and ts       stereoMatching.h:182-188, 201, 320-326
  *                         (dispOptimize cpp:1108-1128, selectTopCostFromVolumn h:2405-2461,
  *                          genDispFromTopCostVm2 cpp:1514-1885)
@@ -311,7 +313,7 @@ SM_API sm_status sm_run(sm_ctx* ctx, int32_t n, float reg_lambda, int16_t* disp_
  * ("cbca_v_norm_scan@1"); the new launches are "pyr_down@<destination level>" and "solve_all_pyr[_r]".
  * sm_aws_config, sm_bf_config, sm_gfnl_config, sm_cbca_double_config (arm_l2 and arm_l_out2 divided by 2^s) and
  * sm_cbca_intersect_config apply to every level, whichever order they and this call come in; a level that cannot
- * take a setting fails that call with the level named and every level unchanged.  sm_vmtop_config,
+ * take a setting fails that call with the level named and every level unchanged.  sm_so_config, sm_vmtop_config,
  * sm_refine_ext_config, sm_refine_da_config, sm_refine_outlier_config and sm_eval_config concern level 0 only.  The staged calls keep their contracts
  * (sm_solve_all refuses py_lev != 1; sm_solve_all_pyr takes one context per level).
  * Checked before any device call: py_lvl outside [1, 8] and a level that sm_create would refuse (rows or cols < 2,
@@ -399,6 +401,33 @@ SM_API sm_status sm_bf_config(sm_ctx* ctx, int32_t ksize_v, int32_t ksize_u);
  * window and the 0.5 / 0.5 blend are fixed.  Applies from the next sm_cost_calculate / sm_run.  SM_EINVAL on
  * a value that is not finite or on a context whose aggregation is not SM_AGG_GFNL. */
 SM_API sm_status sm_gfnl_config(sm_ctx* ctx, float var_thresh);
+
+/* Which scan-line optimiser dispOptimize's "so" branch runs: the reference holds four and chooses one by which call
+ * is commented in (cpp:1096-1100).
+ *   SM_SO_L2R  so (cpp:6272-6394), the shipped call: left to right along the rows, Pn2 = 1.2, Pn3 = 3.6.
+ *   SM_SO_R2L  so_R2L (cpp:6683-6826): columns W-2 .. 0 with prev = vm(v, u+1), the discontinuity between I(v, u) and
+ *              I(v, u+1), vm(v, u)[d] += cost_min in place, the backtrack from the first minimum of column 0 towards
+ *              W-1.  Pn2 = 0.3, Pn3 = 0.9.
+ *   SM_SO_T2D  so_T2D (cpp:6580-6681): per column, rows 1 .. H-1 with prev = vm(v-1, u), the discontinuity between
+ *              I(v, u) and I(v-1, u), vm(v, u)[d] += (cost_min - c_min) with c_min = the row minimum + Pn3 (one
+ *              rounded difference, one rounded sum; accumulated costs go negative), the backtrack upwards from the
+ *              first minimum of the last row.  Pn2 = 0.3, Pn3 = 0.9.  The reference runs it on a clone (vm_res,
+ *              cpp:1095): vm[view] is left untouched, with keep_final_volume too.
+ * All three read the left colour image for both views, try prev[d], prev[d-1] + Pn2, prev[d+1] + Pn2, min + Pn3 in
+ * that order on strict <, take the first index of a minimum, and halve Pn2 and Pn3 where the mean absolute channel
+ * difference to the scan's previous pixel is > 15.  pn2 / pn3 replace the function's literals; SM_SO_PN_DEFAULT
+ * keeps them.  so_change (cpp:6419-6578) is not built: it reads DP before anything has written it.
+ * Not sm_params fields (the struct keeps its size): SM_SO_L2R with 1.2 / 3.6 by default, takes effect from the next
+ * sm_disp_optimize / sm_run; with a pyramid the call concerns level 0 only.  keep_final_volume: SM_SO_R2L leaves its
+ * accumulated volume in vm[view], as so does.  The eval table's stage 0 keeps the name "so" (cpp:1102).  Every
+ * refusal that exists with "so" holds for all variants.  The maps are the same for every schedule.  Profile names:
+ * "so_r2l[_r]", "so_t2d[_r]".  SM_EINVAL, with the argument named in sm_last_error, for a variant outside [0, 2], a
+ * penalty that is neither SM_SO_PN_DEFAULT nor finite and >= +0, or a context whose optimization is not SM_OPT_SO
+ * (unless the call is the all-default one: SM_SO_L2R, SM_SO_PN_DEFAULT, SM_SO_PN_DEFAULT); the arguments are checked
+ * without a device. */
+enum { SM_SO_L2R = 0, SM_SO_R2L = 1, SM_SO_T2D = 2 };
+#define SM_SO_PN_DEFAULT (-1.0f)      /* the chosen function's own literals */
+SM_API sm_status sm_so_config(sm_ctx* ctx, int32_t variant, float pn2, float pn3);
 
 /* dispOptimize's Do_vmTop branch (cpp:1108-1128), the candidate-disparity selection: after "sgm" or "" every pixel
  * keeps the `num` (vmTop_Num = M, main:62) cheapest disparities whose cost is < firstV * thres (vmTop_thres =

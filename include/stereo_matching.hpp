@@ -353,6 +353,11 @@ class StereoMatching {
     // float ratio, the filler chosen per class by Parameters::interpolateType) instead of regionVote_my
     inline static bool LRC_CLASSIFY = false;
     inline static bool RV_COMBINE_BG = false;
+    // which scan-line optimiser dispOptimize's "so" branch calls (cpp:1096-1100; sm_so_config): SM_SO_L2R = so (the
+    // shipped call), SM_SO_R2L = so_R2L (cpp:6683-6826), SM_SO_T2D = so_T2D (cpp:6580-6681, on a clone: vm[i] stays
+    // as aggregated).  SO_PN2 / SO_PN3 replace the chosen function's literals (SM_SO_PN_DEFAULT keeps them)
+    inline static int SO_VARIANT = SM_SO_L2R;
+    inline static float SO_PN2 = SM_SO_PN_DEFAULT, SO_PN3 = SM_SO_PN_DEFAULT;
     // the reference's err txt (saveFromDisp -> calErr after dispOptimize and after refine()'s stages; sm_eval_config):
     // with DT given, the table is built on the GPU while dispOptimize and refine() run; stageErrors() returns its rows
     inline static bool Do_stageErrors = false;
@@ -684,6 +689,8 @@ class StereoMatching {
                   "sm_refine_outlier_config");
             lrc_on_ = LRC_CLASSIFY;
         }
+        if (optimization == "so" && (SO_VARIANT != SM_SO_L2R || SO_PN2 != SM_SO_PN_DEFAULT || SO_PN3 != SM_SO_PN_DEFAULT))
+            check(sm_so_config(ctx_, SO_VARIANT, SO_PN2, SO_PN3), "sm_so_config");
         if (Do_stageErrors && !DT.empty()) {
             if (DT.depth() != CV_32F || DT.rows != h_ || DT.cols != w_) throw std::invalid_argument("Do_stageErrors: DT must be CV_32F H x W");
             const float th = (float)param.errorThreshold;

@@ -31,6 +31,10 @@ REFINE_DA_DEFAULTS = (20, 60, 84, 87)
 # sm_refine_outlier_config's values: disp_mis (DISP_MIS, h:217), interpolate_type (interpolateType, h:310)
 REFINE_OUTLIER_DEFAULTS = (-48, 0)
 OPTIMIZATIONS = {"": 0, "wta": 0, "sgm": 1, "so": 2}
+# sm_so_config: the scan-line optimiser behind optimization "so" (the call commented in at cpp:1096-1100) by the
+# reference's function name, and the value that keeps a function's own Pn2 / Pn3 literals
+SO_VARIANTS = {"so": 0, "so_R2L": 1, "so_T2D": 2}
+SO_PN_DEFAULT = -1.0
 
 
 class sm_params(C.Structure):
@@ -146,6 +150,7 @@ SIGNATURES = [
     ("sm_set_da_edges", C.c_int, [_P, _P]),
     ("sm_refine_outlier_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     ("sm_get_lrc_mask", C.c_int, [_P, _P]),
+    ("sm_so_config", C.c_int, [_P, C.c_int32, C.c_float, C.c_float]),
     ("sm_eval_config", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float)]),
     ("sm_upload_truth", C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
     ("sm_eval_stage_count", C.c_int32, [_P]),

@@ -750,6 +750,25 @@ sm_status sm_aws_config(sm_ctx* c, int32_t radius_v, int32_t radius_u, float gam
     return on_levels(c, [&](sm_ctx* q, int, bool dry) { return aws_config_one(q, radius_v, radius_u, gamma_c, dry); });
 }
 
+sm_status sm_so_config(sm_ctx* c, int32_t variant, float pn2, float pn3) {
+    if (sm_status r = refuse_level(c)) return r;
+    // host state only (a launch carries its constants by value): the arguments are checked before any device call,
+    // so on a machine without a GPU too
+    if (variant < SM_SO_L2R || variant > SM_SO_T2D) return fail(c, SM_EINVAL, "variant must be SM_SO_L2R, SM_SO_R2L or SM_SO_T2D (0, 1, 2)");
+    auto pn_ok = [](float x) { return x == SM_SO_PN_DEFAULT || (std::isfinite(x) && x >= 0 && !std::signbit(x)); };
+    if (!pn_ok(pn2)) return fail(c, SM_EINVAL, "pn2 must be SM_SO_PN_DEFAULT or finite and >= +0 (Pn2)");
+    if (!pn_ok(pn3)) return fail(c, SM_EINVAL, "pn3 must be SM_SO_PN_DEFAULT or finite and >= +0 (Pn3)");
+    const bool all_default = variant == SM_SO_L2R && pn2 == SM_SO_PN_DEFAULT && pn3 == SM_SO_PN_DEFAULT;
+    if (c->p.optimization != SM_OPT_SO && !all_default)
+        return fail(c, SM_EINVAL, "sm_so_config: the context's optimization is not SM_OPT_SO");
+    // so: cpp:6305-6306; so_R2L: cpp:6716-6717; so_T2D: cpp:6607-6608
+    const float d2 = variant == SM_SO_L2R ? 1.2f : 0.3f, d3 = variant == SM_SO_L2R ? 3.6f : 0.9f;
+    c->so_variant = variant;
+    c->so_pn2 = pn2 == SM_SO_PN_DEFAULT ? d2 : pn2;
+    c->so_pn3 = pn3 == SM_SO_PN_DEFAULT ? d3 : pn3;
+    return SM_OK;
+}
+
 sm_status sm_vmtop_config(sm_ctx* c, int32_t enable, int32_t method, int32_t num, float thres, int32_t ts, int32_t has_cir2,
                           int32_t cir3_color_limit) {
     if (sm_status r = refuse_level(c)) return r;

@@ -58,6 +58,9 @@ struct sm_ctx {
     uint8_t* flags1 = nullptr;  // [cap][npix] same for the right image (do_refine)
     uint8_t* so_trace = nullptr;   // [cap][npix][D] "so" choice codes
     uint16_t* so_cidx = nullptr;   // [cap][npix] "so" row-minimum indices
+    // which scan-line optimiser dispOptimize runs (sm_so_config; the call commented in at cpp:1096-1100)
+    int so_variant = SM_SO_L2R;
+    float so_pn2 = 1.2f, so_pn3 = 3.6f;   // the chosen function's Pn2 / Pn3 (so cpp:6305-6306)
     uint32_t* px = nullptr;     // [cap][2][npix] packed BGR, then the pxh and pxv arm-walk planes (same shape)
     // aggregation "GF": three scratch volumes (the SGM sum is the fourth), image planes, per-pixel terms
     float* gf_s = nullptr;      // [3 (+1 without acc)][cap][nvol]

@@ -269,6 +269,8 @@ struct SoArgs {                 // scan-line optimisation "so" (sm_so.hip)
     const uint32_t* px;         // [n][2][H][W] packed BGR (view 0 = I_c[0] is used)
     int16_t* disp;              // [n][H][W]
     int H, W, D, n, keep_final;
+    int r2l;                    // 0: so (left to right); 1: so_R2L (right to left).  launch_so only
+    float pn2, pn3;             // the functions' Pn2 / Pn3 literals (so 1.2 / 3.6; so_R2L, so_T2D 0.3 / 0.9)
 };
 
 constexpr int kMaxPyr = 8;      // PY_LVL limit (sm_solve_all_pyr)
@@ -318,6 +320,8 @@ void launch_region_vote(const int16_t* src, int16_t* dst, const uint32_t* arms, 
 void launch_proper_ipol(const int16_t* src, int16_t* dst, const uint32_t* px, int n, int H, int W, int disp_occ,
                         hipStream_t st);
 void launch_so(const SoArgs& a, hipStream_t st);
+// so_T2D (sm_so_t2d.hip): the programme down the columns; reads vm, writes the map only (keep_final and r2l unused)
+void launch_so_t2d(const SoArgs& a, hipStream_t st);
 void launch_pyr_down(const uint8_t* src, uint8_t* dst, int rows, int cols, int ch, hipStream_t st);
 void launch_pyr_down_f32(const float* src, float* dst, int rows, int cols, hipStream_t st);
 void launch_solve_all_pyr(const PyrArgs& a, hipStream_t st);

@@ -446,10 +446,22 @@ sm_status run_optimize(sm_ctx* c, int view, const Group& G) {
         a.D = p.num_disparities;
         a.n = G.n;
         a.keep_final = p.keep_final_volume;
-        const std::string name = Group::name("so", view);
-        sm_status s = timed(c, G.st, name.c_str(), (double)G.n * c->nvol * (4.0 + 1.0 + (p.keep_final_volume ? 4.0 : 0)),
-                            [&] { sm::launch_so(a, G.st); });
-        if (s) return s;
+        a.pn2 = c->so_pn2;
+        a.pn3 = c->so_pn3;
+        // the call commented in at cpp:1096-1100 (sm_so_config)
+        if (c->so_variant == SM_SO_T2D) {
+            // so_T2D(vm_res, ..) runs on a clone (cpp:1095, 1097): vm[i] is read (4 B per element), never written
+            a.keep_final = 0;
+            const std::string name = Group::name("so_t2d", view);
+            sm_status s = timed(c, G.st, name.c_str(), (double)G.n * c->nvol * 4.0, [&] { sm::launch_so_t2d(a, G.st); });
+            if (s) return s;
+        } else {
+            a.r2l = c->so_variant == SM_SO_R2L;
+            const std::string name = Group::name(a.r2l ? "so_r2l" : "so", view);
+            sm_status s = timed(c, G.st, name.c_str(), (double)G.n * c->nvol * (4.0 + 1.0 + (p.keep_final_volume ? 4.0 : 0)),
+                                [&] { sm::launch_so(a, G.st); });
+            if (s) return s;
+        }
     } else if (!vmtop) {
         const std::string name = Group::name("wta", view);
         sm_status s = timed(c, G.st, name.c_str(), (double)G.n * c->nvol * 4.0 + (double)G.n * c->npix * 2,

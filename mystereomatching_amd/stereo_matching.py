@@ -74,6 +74,11 @@ class StereoMatching:
     # instead of regionVote_my
     LRC_CLASSIFY = False
     RV_COMBINE_BG = False
+    # which scan-line optimiser dispOptimize's "so" branch calls (cpp:1096-1100; sm_so_config): "so" (the shipped
+    # call), "so_R2L" (cpp:6683-6826) or "so_T2D" (cpp:6580-6681, on a clone: vm[i] stays as aggregated); SO_PN
+    # replaces the chosen function's Pn2 / Pn3 literals (None keeps them).  Read with optimization = "so"
+    SO_VARIANT = "so"
+    SO_PN = None
     # the reference's err txt (saveFromDisp -> calErr after dispOptimize and after refine()'s stages; sm_eval_config):
     # True (with DT given) builds the table on the GPU while dispOptimize and refine() run; stageErrors() returns
     # its rows.  Read when an object is constructed, like the switches above
@@ -218,6 +223,12 @@ class StereoMatching:
         if self.aggregation == "GFNL":
             st = self._lib.sm_gfnl_config(ctx, float(self.GFNL_VAR_THRESH))
             _capi.check(self._lib, ctx, st, "sm_gfnl_config")
+        if self.optimization == "so" and (self.SO_VARIANT != "so" or self.SO_PN is not None):
+            if self.SO_VARIANT not in _capi.SO_VARIANTS:
+                raise ValueError(f"SO_VARIANT must be one of {sorted(_capi.SO_VARIANTS)}")
+            pn = (_capi.SO_PN_DEFAULT, _capi.SO_PN_DEFAULT) if self.SO_PN is None else self.SO_PN
+            st = self._lib.sm_so_config(ctx, _capi.SO_VARIANTS[self.SO_VARIANT], float(pn[0]), float(pn[1]))
+            _capi.check(self._lib, ctx, st, "sm_so_config")
         if param.Do_vmTop:
             st = self._lib.sm_vmtop_config(ctx, 1, int(param.vmTop_method), int(param.vmTop_Num), float(param.vmTop_thres),
                                            int(param.ts), int(param.vmTop_hasCir2), int(param.vmTop_cir3_doColorLimit))
@@ -436,6 +447,12 @@ class StereoBatch:
         refine_outlier = overrides.pop("refine_outlier", None)
         # the per-stage error table (sm_eval_config): eval is a dict of eval_config's arguments
         eval_cfg = overrides.pop("eval", None)
+        # the scan-line optimiser behind optimization "so" (sm_so_config): so_variant is the reference's function
+        # name, so_pn = (pn2, pn3) replaces its penalty literals
+        so_variant = overrides.pop("so_variant", "so")
+        so_pn = overrides.pop("so_pn", None)
+        if so_variant not in _capi.SO_VARIANTS:
+            raise ValueError(f"so_variant must be one of {sorted(_capi.SO_VARIANTS)}")
         # the cross-scale pyramid inside run() (sm_pyramid_config): py_lvl = PY_LEV of main_.cpp:131, applied last
         py_lvl = int(overrides.pop("py_lvl", 1))
         p = _capi.default_params(max_disp, rows, cols, **overrides)
@@ -455,6 +472,8 @@ class StereoBatch:
             self.cbca_double_config(True, *dw_args)
         if not intersect:
             self.cbca_intersect_config(False)
+        if so_variant != "so" or so_pn is not None:
+            self.so_config(so_variant, so_pn)
         if refine_ext:
             self.refine_ext_config(**dict(refine_ext))
         if refine_da:
@@ -684,6 +703,16 @@ class StereoBatch:
         out = np.empty(self.shape[:2], np.uint8)
         _capi.check(self._lib, self._ctx, self._lib.sm_get_da_edges(self._ctx, _capi.ptr(out)), "get_da_edges")
         return out
+
+    def so_config(self, variant: str = "so", pn=None):
+        """sm_so_config: the scan-line optimiser that optimization "so" runs from the next run on — "so", "so_R2L"
+        or "so_T2D" (the reference's function names) — and, with pn = (pn2, pn3), its penalties instead of the
+        function's literals."""
+        if variant not in _capi.SO_VARIANTS:
+            raise ValueError(f"variant must be one of {sorted(_capi.SO_VARIANTS)}")
+        pn2, pn3 = (_capi.SO_PN_DEFAULT, _capi.SO_PN_DEFAULT) if pn is None else pn
+        st = self._lib.sm_so_config(self._ctx, _capi.SO_VARIANTS[variant], float(pn2), float(pn3))
+        _capi.check(self._lib, self._ctx, st, "so_config")
 
     def refine_outlier_config(self, classify: bool = False, disp_mis: int = _capi.REFINE_OUTLIER_DEFAULTS[0],
                               rv_combine: bool = False, interpolate_type: int = _capi.REFINE_OUTLIER_DEFAULTS[1]):

@@ -2,12 +2,15 @@
 """Evaluate the GPU pipeline on a Middlebury-layout dataset, the way main_.cpp does (main:26-178).
 
 usage: tools/sm_eval.py ROOT [--objects teddy cones ...] [--refine] [--pyr L] [--device N] [--stages]
+                        [--so-variant so|so_R2L|so_T2D]
 
 For each object: load (mystereomatching_amd.dataset), Parameters(maxdisp, ...), costCalculate per
 pyramid level, SolveAll(PY_LEV, 0.3), dispOptimize [, refine], then calErr over nonocc / all /
 disc at t = 1 (errorThreshold, h:225) and t = 2 (BASELINE's bad-2.0).  Prints one JSON line per
 object.  --stages also prints the reference's err-txt lines (calErr after dispOptimize and after every stage of
 refine(), h:1756-1817), one per stage, from the table the GPU builds while the pipeline runs (sm_eval_config).
+--so-variant runs the scan-line optimiser instead of SGM: "so", or one of the calls dispOptimize keeps commented out
+(cpp:1096-1100), "so_R2L" or "so_T2D" (sm_so_config).
 No dataset ships with this repository; point ROOT at a local Middlebury copy.
 """
 import argparse
@@ -26,9 +29,20 @@ def run(sample, refine, levels, device):
     return run_stages(sample, refine, levels, device, False)[:2]
 
 
-def run_stages(sample, refine, levels, device, stages=True):
-    """run() plus, with `stages`, calErr's err-txt lines of level 0 (one per stage)."""
-    StereoMatching.costcalculation, StereoMatching.aggregation, StereoMatching.optimization = "censusGrad", "CBCA", "sgm"
+def run_stages(sample, refine, levels, device, stages=True, so_variant=None):
+    """run() plus, with `stages`, calErr's err-txt lines of level 0 (one per stage).  so_variant: the scan-line
+    optimiser of that name instead of SGM."""
+    saved = (StereoMatching.optimization, StereoMatching.SO_VARIANT)
+    StereoMatching.costcalculation, StereoMatching.aggregation = "censusGrad", "CBCA"
+    StereoMatching.optimization = "so" if so_variant else "sgm"
+    StereoMatching.SO_VARIANT = so_variant or "so"
+    try:
+        return _run_stages(sample, refine, levels, device, stages)
+    finally:   # the selectors are process-wide statics: a later caller does not inherit the variant
+        StereoMatching.optimization, StereoMatching.SO_VARIANT = saved
+
+
+def _run_stages(sample, refine, levels, device, stages):
     StereoMatching.Do_refine = refine
     StereoMatching.Do_stageErrors = bool(stages) and sample.gt is not None
     masks = sample.masks if stages else {}
@@ -63,12 +77,16 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--dataset", default="MD")
     ap.add_argument("--stages", action="store_true", help="print calErr's err-txt line of every stage")
+    ap.add_argument("--so-variant", choices=["so", "so_R2L", "so_T2D"], default=None,
+                    help="the scan-line optimiser of that name instead of SGM (sm_so_config)")
     a = ap.parse_args()
     for obj in a.objects:
         s = dataset.load(a.root, obj, a.dataset)
-        dp, t, lines = run_stages(s, a.refine, a.pyr, a.device, a.stages)
+        dp, t, lines = run_stages(s, a.refine, a.pyr, a.device, a.stages, a.so_variant)
         out = {"object": obj, "H": s.lgray.shape[0], "W": s.lgray.shape[1], "D": s.max_disp + 1,
                "refine": a.refine, "py_lev": a.pyr, "seconds": round(t, 4)}
+        if a.so_variant:
+            out["so_variant"] = a.so_variant
         if s.gt is not None:
             for t_ in (1.0, 2.0):
                 for r, (pbm, rms) in cal_err_regions(dp, s.gt, s.masks, t_).items():

@@ -205,9 +205,7 @@ __global__ __launch_bounds__(256) void k_aws_agg(const AwsArgs a) {
         const bool ok = lor ? u + d < W : u - d >= 0;
         const size_t e = ((size_t)v * W + u) * D + d;
         if (!ok && !a.solve_all) continue;   // `out` holds the raw cost already
-        float val = ok ? num[j] / den[j] : raw[e];
-        if (a.solve_all) val = 0.f + a.scale * val;   // SolveAll's 0 + w q (cpp:2189-2201)
-        out[e] = val;
+        out[e] = solve_all_store(ok ? num[j] / den[j] : raw[e], a.solve_all, a.scale);
     }
 }
 

@@ -9,6 +9,7 @@
 //   (1,120,924,085 inputs, 0 mismatches) on the build host, and the device build is checked
 //   over the same range on the GPU box (tests/test_gpu_parity.py::test_device_expf_exhaustive).
 // * sm_reflect101: OpenCV borderInterpolate(BORDER_REFLECT_101) (copyMakeBorder, h:870-871).
+// * solve_all_store: SolveAll's weight, fused into the aggregations' last stores.
 // * wave64 reductions built on DPP + gfx950 permlane swaps (no LDS round trip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -89,6 +90,15 @@ __host__ __device__ inline int reflect101(int p, int len) {
 __device__ __forceinline__ int xcd_swizzle(int orig, int nwg) {
     const int xcd = orig & 7, idx = orig >> 3, q = nwg >> 3, r = nwg & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// What an aggregation's last store writes.  Under sm_run the launch carries SolveAll (`solve_all`
+// set, the same in every lane), whose `sum = 0; sum += w * q` (cpp:2189-2201) is 0 + w q, not
+// w q: the two differ for q = -0.
+__device__ __forceinline__ float solve_all_store(float q, int solve_all, float scale) {
+    if (!solve_all) return q;
+    const float wq = scale * q;
+    return 0.f + wq;
 }
 
 // Buffer-instruction access (gfx9 resource word 3 = 0x00020000, 32-bit data).  The range limit

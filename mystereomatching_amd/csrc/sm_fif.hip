@@ -198,8 +198,7 @@ __global__ __launch_bounds__(256) void k_fif_sweep(const FifArgs a) {
 #pragma unroll
         for (int k = 0; k < K; k++) {
             if (SECOND) {
-                o[k] = (t.f[s][k] + L[k]) - t.a[s][k];
-                if (a.solve_all) o[k] = 0.f + a.scale * o[k];   // SolveAll's 0 + w q (cpp:2189-2201)
+                o[k] = solve_all_store((t.f[s][k] + L[k]) - t.a[s][k], a.solve_all, a.scale);
             } else {
                 o[k] = L[k];
             }

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sm_box_sweep.h"   // line_block only: this file's filter is the reference's CumSum, not OpenCV's
 #include "sm_device.h"
 #include "sm_kernels.h"
 
@@ -205,16 +206,9 @@ __global__ __launch_bounds__(256) void k_gf_pix(const float* __restrict__ planes
 // ---------------------------------------------------------------------------------------------
 template <bool HORIZ, int MODE>   // MODE 0: first box (from p), MODE 1: second box (from a, b)
 __global__ __launch_bounds__(64) void k_gf_sweep(const GfArgs a) {
-    const int lane = threadIdx.x;
-    const int nchunks = (a.D + 63) >> 6;
-    const int lines = HORIZ ? a.H : a.W;
-    const int blk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int b = blk / (lines * nchunks);
-    const int lc = blk - b * lines * nchunks;
-    const int line = lc / nchunks, chunk = lc - line * nchunks;
-    const int d = chunk * 64 + lane;
-    const bool live = d < a.D;
-    const int dd = live ? d : a.D - 1;
+    const LineBlock B = line_block(HORIZ ? a.H : a.W, a.D);
+    const int b = B.pair, line = B.line, dd = B.dd;
+    const bool live = B.live;
     const size_t npix = (size_t)a.H * a.W;
     const int len = HORIZ ? a.W : a.H;
     const size_t pstep = HORIZ ? 1 : (size_t)a.W;            // pixels between positions
@@ -319,11 +313,7 @@ __global__ __launch_bounds__(64) void k_gf_sweep(const GfArgs a) {
                     const float m = ma * (float)q[c];
                     out += m;
                 }
-                if (a.solve_all) {   // SolveAll fused (sm_run): its `sum = 0; sum += w * v`
-                    float sum = 0.f;
-                    sum += a.scale * out;
-                    out = sum;
-                }
+                out = solve_all_store(out, a.solve_all, a.scale);
                 if (live) a.vm[vo] = out;
             }
         }

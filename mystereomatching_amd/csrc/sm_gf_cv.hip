@@ -3,31 +3,30 @@
 // (stereoMatching.cpp:4513, `//#define MY_GUIDE` at h:38; constants h:297-298).  The restated
 // algorithm (oracle/sm_oracle_agg.c, smo_guided_filter_cv) is He et al.'s colour guided filter in
 // the structure of ximgproc's GuidedFilterImpl, every mean an OpenCV normalised box filter with
-// BORDER_REFLECT whose row and column sums run in double:
+// BORDER_REFLECT, 19 x 19 (sm_box_sweep.h: the filter, shared with "BF"):
 //
-//   box(x)(y, u) = (float)(s0 * 1/361),  s0 = SUM_y + RS(y + r),  SUM_{y+1} = s0 - RS(y - r)
-//   RS(y, u)     = running row sum: the first 19 reflected values, then += (double)x[u + 10 + ...]
 //   Sigma        = box(I_i I_j) - mean_I_i mean_I_j (+ eps on the diagonal), inverted by cofactors
 //   alpha_c      = sum_k Sigma^-1(c, k) (box(p I_k) - mean_p mean_I_k),  beta = mean_p - alpha . mean_I
 //   q            = box(beta) + sum_c box(alpha_c) I_c
 //
 // gfx950 mapping.  The p-independent terms (mean_I and Sigma^-1 per pixel, 9 floats) come from
 // nine image planes, row-summed by one thread per row (k_gfcv_img_rows), column-summed by one
-// thread per plane and column (k_gfcv_img_cols), Sigma inverted per pixel (k_gfcv_pix).  The volume work is four line
-// sweeps over [H][W][D] with lane = disparity and one wave per (line, 64-disparity chunk), each
-// carrying four channels:
+// thread per plane and column (k_gfcv_img_cols), Sigma inverted per pixel (k_gfcv_pix).  The
+// volume work is four of the header's line sweeps over [H][W][D], each carrying four channels:
 //   R0: row sums of (p, p B, p G, p R)          -> RS (four double volumes)
 //   C0: column sums -> mean_p, cov, alpha, beta -> AB (four float volumes)
 //   R1: row sums of (alpha_0..2, beta)           -> RS
 //   C1: column sums -> q                         -> vm  [+ SolveAll's 0 + w q]
 // The double intermediates are what OpenCV's FilterEngine keeps between its row and column
 // filters; a row chain (RowSum's running update) can only run sequentially along the whole row,
-// so the row sums round-trip HBM.  Every operation is the restatement's, in its order
-// (-ffp-contract=off: no fused multiply-adds), so the volume is bit-exact to the oracle.
+// so the row sums round-trip HBM.  The float products and sums around the box means are the
+// restatement's, in its order (-ffp-contract=off: no fused multiply-adds), so the volume is
+// bit-exact to the oracle.
 #include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sm_box_sweep.h"
 #include "sm_device.h"
 #include "sm_kernels.h"
 
@@ -40,9 +39,9 @@ constexpr int GC_K = 2 * GC_R + 1;   // box size
 #ifndef SM_GFCV_PF
 #define SM_GFCV_PF 3     // rows of row sums prefetched ahead by the column sweeps (divides 18)
 #endif
-
-// OpenCV borderInterpolate(BORDER_REFLECT) for len >= GC_R (one reflection suffices)
-__device__ __forceinline__ int refl(int p, int len) { return p < 0 ? -p - 1 : (p >= len ? 2 * len - 1 - p : p); }
+#ifndef SM_GFCV_T
+#define SM_GFCV_T 4   // positions per prefetched tile of the row sweeps (two tiles in flight)
+#endif
 
 // image planes 0..8: B, G, R, BB, BG, BR, GG, GR, RR (float products of the float guide)
 __device__ __forceinline__ float gc_plane(uint32_t w, int k) {
@@ -60,7 +59,7 @@ __device__ __forceinline__ float gc_plane(uint32_t w, int k) {
     }
 }
 
-// one thread per (pair, plane, row): RowSum<float, double> over the reflected row into rs
+// one thread per (pair, plane, row): the plane's row sums into rs
 __global__ __launch_bounds__(256) void k_gfcv_img_rows(const uint32_t* __restrict__ px, size_t px_pair_stride,
                                                        double* __restrict__ rs, int H, int W, int n) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -68,18 +67,13 @@ __global__ __launch_bounds__(256) void k_gfcv_img_rows(const uint32_t* __restric
     const int y = t % H, k = (t / H) % 9, b = t / (9 * H);
     const uint32_t* row = px + (size_t)b * px_pair_stride + (size_t)y * W;
     double* out = rs + (((size_t)b * 9 + k) * H + y) * W;
-    double s = 0;
-    for (int i = 0; i < GC_K; i++) s += (double)gc_plane(row[refl(i - GC_R, W)], k);
-    out[0] = s;
-    for (int i = 0; i < W - 1; i++) {
-        s += (double)gc_plane(row[refl(i + GC_K - GC_R, W)], k) - (double)gc_plane(row[refl(i - GC_R, W)], k);
-        out[i + 1] = s;
-    }
+    box_row_sweep<1, Reflect, SM_GFCV_T, GC_K>(
+        W, GC_K, [&](int u, float (&x)[1]) { x[0] = gc_plane(row[u], k); }, [&](int u, const double (&S)[1]) { out[u] = S[0]; });
 }
 
-// one thread per (pair, plane, column): ColumnSum<double, float> of the plane into pix[b][k]
-// (the means; planes 3..8 are replaced by Sigma^-1 in k_gfcv_pix).  The next rows' sums are
-// loaded while the current ones are added (a column walk is a chain of dependent adds).
+// one thread per (pair, plane, column): the plane's box means into pix[b][k] (planes 3..8 are
+// replaced by Sigma^-1 in k_gfcv_pix).  The tiled column form (a column walk is a chain of
+// dependent adds: the next rows' sums are loaded while the current ones are added).
 __global__ __launch_bounds__(256) void k_gfcv_img_cols(const double* __restrict__ rs, float* __restrict__ pix, int H, int W,
                                                        int n) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -88,35 +82,9 @@ __global__ __launch_bounds__(256) void k_gfcv_img_cols(const double* __restrict_
     const size_t npix = (size_t)H * W;
     const double* base = rs + ((size_t)b * 9 + k) * npix + x;
     float* out = pix + ((size_t)b * 9 + k) * npix + x;
-    const double scale = 1. / (GC_K * GC_K);
-    double SUM = 0;
-    for (int i = 0; i < GC_K - 1; i++) SUM += base[(size_t)refl(i - GC_R, H) * W];
-    constexpr int U = 4;
-    double sp[U], sm[U], np[U], nm[U];
-    auto fetch = [&](double (&p)[U], double (&m)[U], int y0) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int y = min(y0 + u, H - 1);
-            p[u] = base[(size_t)refl(y + GC_R, H) * W];
-            m[u] = base[(size_t)refl(y - GC_R, H) * W];
-        }
-    };
-    fetch(np, nm, 0);
-    for (int y0 = 0; y0 < H; y0 += U) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            sp[u] = np[u];
-            sm[u] = nm[u];
-        }
-        if (y0 + U < H) fetch(np, nm, y0 + U);
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (y0 + u >= H) break;
-            const double s0 = SUM + sp[u];
-            out[(size_t)(y0 + u) * W] = (float)(s0 * scale);
-            SUM = s0 - sm[u];
-        }
-    }
+    box_col_sweep_tiled<1, Reflect, SM_GFCV_T>(
+        H, GC_K, 1. / (GC_K * GC_K), [&](int y, double (&v)[1]) { v[0] = base[(size_t)y * W]; },
+        [&](int y, const float (&m)[1]) { out[(size_t)y * W] = m[0]; });
 }
 
 // per pixel: Sigma = box(I_i I_j) - m_i m_j (+ eps on the diagonal) and its inverse by the
@@ -161,130 +129,69 @@ __global__ __launch_bounds__(256) void k_gfcv_pix(float* __restrict__ pix, int H
     pl[8 * npix] = b22 / det;
 }
 
-#ifndef SM_GFCV_T
-#define SM_GFCV_T 4   // positions per prefetched tile of the row sweeps (two tiles in flight)
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // Row sweep: one wave per (pair, row, chunk), lane = disparity.  MODE 0 reads p (vm) and the
-// guide, MODE 1 reads alpha_0..2, beta (AB).  Ext position i (column refl(i - r)) enters the
-// running sums; from i = k on, position i - k leaves (read again: it was loaded k positions ago,
-// an L1 / L2 hit).
+// guide, MODE 1 reads alpha_0..2, beta (AB).
 // ---------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(64) void k_gfcv_rows(const GfCvArgs a) {
-    constexpr int T = SM_GFCV_T;
-    const int lane = threadIdx.x;
-    const int nchunks = (a.D + 63) >> 6;
-    const int blk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int b = blk / (a.H * nchunks);
-    const int lc = blk - b * a.H * nchunks;
-    const int y = lc / nchunks, chunk = lc - y * nchunks;
-    const int d = chunk * 64 + lane;
-    const bool live = d < a.D;
-    const int dd = live ? d : a.D - 1;
+    const LineBlock B = line_block(a.H, a.D);
     const int W = a.W, D = a.D;
     const size_t npix = (size_t)a.H * W;
     const size_t nvol = npix * D;
-    const size_t row0 = ((size_t)b * npix + (size_t)y * W) * D + dd;   // element (b, y, 0, dd)
-    const uint32_t* gw = a.px + (size_t)b * a.px_pair_stride + (size_t)y * W;
-    double* rs = a.rs;
-    const size_t rs_plane = (size_t)a.cap * nvol;   // doubles between channel planes
-    const float* ab = a.ab;
-    const size_t ab_plane = (size_t)a.cap * nvol;
-    const int L = W + 2 * GC_R;   // ext positions
+    const size_t row0 = ((size_t)B.pair * npix + (size_t)B.line * W) * D;   // element (b, y, 0, 0)
+    const uint32_t* gw = a.px + (size_t)B.pair * a.px_pair_stride + (size_t)B.line * W;
+    const float* vm = a.vm + row0 + B.dd;
+    const float* ab = a.ab + row0 + B.dd;
+    double* rs = a.rs + row0 + B.d;
+    const size_t plane = (size_t)a.cap * nvol;   // elements between the channel planes of RS and AB
 
-    auto fetch = [&](int i, float (&x)[4]) {
-        const int u = refl(i - GC_R, W);
-        const size_t e = row0 + (size_t)u * D;
-        if (MODE == 0) {
-            const float p = a.vm[e];
-            const uint32_t w = gw[u];
-            x[0] = p;
-            x[1] = p * (float)(w & 0xffu);             // mul(src, guideCn[0]) (covSrcGuide)
-            x[2] = p * (float)((w >> 8) & 0xffu);
-            x[3] = p * (float)((w >> 16) & 0xffu);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; c++) x[c] = ab[c * ab_plane + e];
-        }
-    };
-    struct Tile {
-        float in[T][4];
-        float out[T][4];
-    };
-    auto load = [&](Tile& t, int i0) {
-#pragma unroll
-        for (int s = 0; s < T; s++) {
-            const int i = min(i0 + s, L - 1);
-            fetch(i, t.in[s]);
-            fetch(max(i - GC_K, 0), t.out[s]);
-        }
-    };
-    double S[4] = {0, 0, 0, 0};
-    auto process = [&](const Tile& t, int i0) {
-#pragma unroll
-        for (int s = 0; s < T; s++) {
-            const int i = i0 + s;
-            if (i >= L) break;   // wave-uniform
-            if (i < GC_K) {
-#pragma unroll
-                for (int c = 0; c < 4; c++) S[c] += (double)t.in[s][c];
+    box_row_sweep<4, Reflect, SM_GFCV_T, GC_K>(
+        W, GC_K,
+        [&](int u, float (&x)[4]) {
+            const size_t e = (size_t)u * D;
+            if (MODE == 0) {
+                const float p = vm[e];
+                const uint32_t w = gw[u];
+                x[0] = p;
+                x[1] = p * (float)(w & 0xffu);             // mul(src, guideCn[0]) (covSrcGuide)
+                x[2] = p * (float)((w >> 8) & 0xffu);
+                x[3] = p * (float)((w >> 16) & 0xffu);
             } else {
 #pragma unroll
-                for (int c = 0; c < 4; c++) S[c] += (double)t.in[s][c] - (double)t.out[s][c];
+                for (int c = 0; c < 4; c++) x[c] = ab[c * plane + e];
             }
-            if (i >= GC_K - 1 && live) {
-                const size_t e = row0 - dd + d + (size_t)(i - (GC_K - 1)) * D;
+        },
+        [&](int u, const double (&S)[4]) {
+            if (!B.live) return;
 #pragma unroll
-                for (int c = 0; c < 4; c++) rs[c * rs_plane + e] = S[c];
-            }
-        }
-    };
-    Tile ta, tb;
-    load(ta, 0);
-    for (int i0 = 0; i0 < L; i0 += 2 * T) {
-        load(tb, i0 + T);
-        process(ta, i0);
-        if (i0 + T >= L) break;
-        load(ta, i0 + 2 * T);
-        process(tb, i0 + T);
-    }
+            for (int c = 0; c < 4; c++) rs[c * plane + (size_t)u * D] = S[c];
+        });
 }
 
 // ---------------------------------------------------------------------------------------------
-// Column sweep: one wave per (pair, column, chunk).  SUM starts as the first k - 1 reflected
-// rows' row sums; output row y adds row y + r, stores (float)(s0 / 361) and drops row y - r.
+// Column sweep: one wave per (pair, column, chunk), lane = disparity.
 // MODE 0: mean_p, box(p I_c) -> cov, alpha, beta -> AB.  MODE 1: box(alpha), box(beta) -> q -> vm.
 // ---------------------------------------------------------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(64) void k_gfcv_cols(const GfCvArgs a) {
-    const int lane = threadIdx.x;
-    const int nchunks = (a.D + 63) >> 6;
-    const int blk = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int b = blk / (a.W * nchunks);
-    const int lc = blk - b * a.W * nchunks;
-    const int u = lc / nchunks, chunk = lc - u * nchunks;
-    const int d = chunk * 64 + lane;
-    const bool live = d < a.D;
-    const int dd = live ? d : a.D - 1;
+    const LineBlock B = line_block(a.W, a.D);
     const int H = a.H, W = a.W, D = a.D;
     const size_t npix = (size_t)H * W;
     const size_t nvol = npix * D;
-    const size_t col0 = ((size_t)b * npix + u) * D + dd;   // element (b, 0, u, dd)
+    const size_t col0 = ((size_t)B.pair * npix + B.line) * D;   // element (b, 0, u, 0)
     const size_t rstep = (size_t)W * D;
-    const double* rs = a.rs;
-    const size_t rs_plane = (size_t)a.cap * nvol;
-    float* ab = a.ab;
-    const size_t ab_plane = (size_t)a.cap * nvol;
-    const float* pix = a.pix + (size_t)b * 9 * npix + u;
-    const uint32_t* gw = a.px + (size_t)b * a.px_pair_stride + u;
-    const double scale = 1. / (GC_K * GC_K);
+    const double* rs = a.rs + col0 + B.dd;
+    float* ab = a.ab + col0 + B.d;
+    float* vm = a.vm + col0 + B.d;
+    const size_t plane = (size_t)a.cap * nvol;   // elements between the channel planes of RS and AB
+    const float* pix = a.pix + (size_t)B.pair * 9 * npix + B.line;
+    const uint32_t* gw = a.px + (size_t)B.pair * a.px_pair_stride + B.line;
 
     // output row y from the box means m (MODE 0: alpha, beta -> AB; MODE 1: q -> vm)
     auto emit = [&](int y, const float (&m)[4]) {
         const size_t po = (size_t)y * W;
-        const size_t e = col0 - dd + d + (size_t)y * rstep;
+        const size_t e = (size_t)y * rstep;
         if (MODE == 0) {
             const float mI[3] = {pix[0 * npix + po], pix[1 * npix + po], pix[2 * npix + po]};
             const float iv[6] = {pix[3 * npix + po], pix[4 * npix + po], pix[5 * npix + po],
@@ -315,11 +222,11 @@ __global__ __launch_bounds__(64) void k_gfcv_cols(const GfCvArgs a) {
                 const float mm = al[g] * mI[g];
                 be = be - mm;
             }
-            if (live) {
-                ab[0 * ab_plane + e] = al[0];
-                ab[1 * ab_plane + e] = al[1];
-                ab[2 * ab_plane + e] = al[2];
-                ab[3 * ab_plane + e] = be;
+            if (B.live) {
+                ab[0 * plane + e] = al[0];
+                ab[1 * plane + e] = al[1];
+                ab[2 * plane + e] = al[2];
+                ab[3 * plane + e] = be;
             }
         } else {
             const uint32_t w = gw[po];
@@ -330,58 +237,19 @@ __global__ __launch_bounds__(64) void k_gfcv_cols(const GfCvArgs a) {
                 const float mm = m[g] * I[g];
                 q = q + mm;
             }
-            if (a.solve_all) {   // SolveAll fused (sm_run): its `sum = 0; sum += w * v`
-                float sum = 0.f;
-                sum += a.scale * q;
-                q = sum;
-            }
-            if (live) a.vm[e] = q;
+            q = solve_all_store(q, a.solve_all, a.scale);
+            if (B.live) vm[e] = q;
         }
     };
-    double SUM[4] = {0, 0, 0, 0};
-    // The row sums leaving the window (row y - r) are the ones that entered it 2r = 18 rows
-    // earlier: a register ring of 18 rows x 4 channels keeps them, so every RS element is read
-    // once (the tiled form, tools/experiments/gfcv_cols_tiled.patch, read it twice, the second
-    // time 18 rows later, past L2).
-    // ring[i] starts as row refl(i - r), the rows the first 18 outputs drop; slot y mod 18.
-    constexpr int RK = GC_K - 1, PF = SM_GFCV_PF;
-    static_assert(RK % PF == 0, "prefetch slots repeat with the ring");
-    double ring[RK][4], nx[PF][4];
+    // The ring form: the tiled form (tools/experiments/gfcv_cols_tiled.patch) read the leaving row
+    // a second time 18 rows later, past L2.
+    box_col_sweep_ring<4, Reflect, GC_K, SM_GFCV_PF>(
+        H, 1. / (GC_K * GC_K),
+        [&](int y, double (&x)[4]) {
 #pragma unroll
-    for (int i = 0; i < RK; i++) {
-        const size_t e = col0 + (size_t)refl(i - GC_R, H) * rstep;
-#pragma unroll
-        for (int c = 0; c < 4; c++) ring[i][c] = rs[c * rs_plane + e];
-    }
-#pragma unroll
-    for (int i = 0; i < RK; i++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) SUM[c] += ring[i][c];
-    auto fetch = [&](double (&x)[4], int y) {
-        const size_t ep = col0 + (size_t)refl(min(y, H - 1) + GC_R, H) * rstep;
-#pragma unroll
-        for (int c = 0; c < 4; c++) x[c] = rs[c * rs_plane + ep];
-    };
-#pragma unroll
-    for (int k = 0; k < PF; k++) fetch(nx[k], k);
-    for (int y0 = 0; y0 < H; y0 += RK) {
-#pragma unroll
-        for (int s = 0; s < RK; s++) {
-            const int y = y0 + s;
-            if (y >= H) break;   // wave-uniform
-            float m[4];
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const double sp = nx[s % PF][c];
-                const double s0 = SUM[c] + sp;
-                m[c] = (float)(s0 * scale);
-                SUM[c] = s0 - ring[s][c];
-                ring[s][c] = sp;
-            }
-            fetch(nx[s % PF], y + PF);
-            emit(y, m);
-        }
-    }
+            for (int c = 0; c < 4; c++) x[c] = rs[c * plane + (size_t)y * rstep];
+        },
+        emit);
 }
 
 }  // namespace

@@ -285,13 +285,7 @@ __device__ __forceinline__ void nl_down_compute(const NlDownBlock<K>& B, const N
         if (d == 0) a.ofin[r.x] = fo;
         carry = fin;
         carry_o = fo;
-        float out = (float)fin / (float)fo;
-        if (a.solve_all) {   // SolveAll fused (sm_run): its `sum = 0; sum += w * v`
-            float sum = 0.f;
-            sum += a.scale * out;
-            out = sum;
-        }
-        a.vm[(size_t)r.x * P + d] = out;
+        a.vm[(size_t)r.x * P + d] = solve_all_store((float)fin / (float)fo, a.solve_all, a.scale);
     }
 }
 
@@ -623,12 +617,7 @@ __global__ __launch_bounds__(64 * (PC_WAVES + PC_SW), 1) void k_nl_down_pc(const
                     if (cc * PC_C + k >= len) break;
                     const double fin = B.fin[k][lane], fo = B.fo[k];
                     const int x = __builtin_amdgcn_readfirstlane(B.x[k]);
-                    float out = (float)fin / (float)fo;
-                    if (a.solve_all) {   // SolveAll fused (sm_run): its `sum = 0; sum += w * v`
-                        float sum = 0.f;
-                        sum += a.scale * out;
-                        out = sum;
-                    }
+                    const float out = solve_all_store((float)fin / (float)fo, a.solve_all, a.scale);
                     const uint32_t row = (uint32_t)x * (uint32_t)P;
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, fin), val_r, dof8, row * 8u, 0);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), vm_r, dof4, row * 4u, 0);

@@ -106,6 +106,17 @@ def test_bf_windows(kv, ku):
             np.testing.assert_array_equal(bits(got[v]), bits(raw[v]))
 
 
+# the largest window on its minimum image (both reflections reach index 0 and n - 1, lines shorter than one
+# tile pair, a ragged second chunk); the tiled column form alone; the row form alone on a one-lane second chunk
+@pytest.mark.parametrize("H,W,D,kv,ku,idx", [(17, 17, 70, 32, 32, 810), (17, 40, 3, 32, 1, 811), (9, 17, 65, 1, 32, 812)])
+def test_bf_windows_at_the_sweeps_limits(H, W, D, kv, ku, idx):
+    """test_bf_windows' assertion at the smallest shapes where the shared line sweeps can still go wrong."""
+    pair, raw = _case(H, W, D - 1, idx)
+    got = _gpu_volumes(pair, H, W, D - 1, ksize=(kv, ku))
+    for v in (0, 1):
+        np.testing.assert_array_equal(bits(got[v]), bits(B.box_filter(raw[v], kv, ku)), err_msg=f"view {v}")
+
+
 def test_bf_window_too_large_for_the_image():
     pair, _ = _case(7, 7, 0, 800)
     assert _gpu_volumes(pair, 7, 7, 0, ksize=(32, 32), expect=_capi.SM_EINVAL) is None

@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=8)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--kernels", default="", help="comma-separated profile-name filter")
-    ap.add_argument("--agg", default="CBCA", help="aggregation (CBCA, GF, NL)")
+    ap.add_argument("--agg", default="CBCA", help="aggregation (CBCA, GF, NL, FIF, AWS, BF, GFNL)")
     ap.add_argument("--copies", type=int, default=1,
                     help="instances per variant, created interleaved (A B A B ...): device allocations fall into "
                          "fast and slow placements (DESIGN §6), so compare medians over several instances")

@@ -122,7 +122,8 @@ typedef enum sm_cost_method {
 typedef enum sm_aggregation {
     SM_AGG_NONE = 0,
     SM_AGG_CBCA = 1,         /* "CBCA" (main:16; cpp:1002-1003) — default */
-    SM_AGG_GF = 2,           /* "GF"  guideFilter (cpp:4492-4516), form chosen by gf_mode; sgm / WTA only */
+    SM_AGG_GF = 2,           /* "GF"  guideFilter (cpp:4492-4516), form chosen by gf_mode.  Costs may be negative or NaN:
+                              * sgm / WTA, and so through sm_create_ex with so_float_minima = 1 */
     SM_AGG_NL = 3,           /* "NL"  non-local MST tree filter (cpp:4892-4917, NL/NLCCA.cpp:27-96) */
     /* 4 is reserved (rejected by sm_create) */
     SM_AGG_FIF = 5,          /* "FIF" full-image guided filter: four weighted sweeps over the volume, form chosen
@@ -135,10 +136,12 @@ typedef enum sm_aggregation {
      * renumber or fill them */
     SM_AGG_BF = 9,           /* "BF" cv::boxFilter(vm[i], vm[i], -1, Size(12, 12)) on every view that exists
                               * (cpp:1023-1043): normalised, BORDER_REFLECT_101, anchor 6, i.e. offsets -6 .. +5;
-                              * window: sm_bf_config.  Costs stay >= +0: every optimiser applies */
+                              * window: sm_bf_config.  Costs stay >= +0 while the sums are exact: every optimiser applies;
+                              * with inexact sums (gradient cost methods, ad_trunc_ad off the 2^-25 grid) so needs
+                              * sm_create_ex with so_float_minima = 1 */
     SM_AGG_GFNL = 10,        /* "GFNL" (cpp:4421-4490): vm[0] = NL where the left gray image's 19 x 19 variance is
                               * < 400 (sm_gfnl_config), else (float)(0.5 NL + 0.5 GF); vm[1] is GF's (do_refine).
-                              * Reads gf_eps, gf_mode, nl_sigma; like GF, sgm / WTA only */
+                              * Reads gf_eps, gf_mode, nl_sigma; like GF, sgm / WTA, and so through sm_create_ex */
 } sm_aggregation;
 
 /* "FIF"'s two forms: */
@@ -254,6 +257,31 @@ typedef struct sm_ctx sm_ctx;
 
 SM_API void sm_params_default(sm_params* p, int32_t max_disp, int32_t rows, int32_t cols);
 SM_API sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device);
+
+/* sm_create with options that are not sm_params fields (the struct keeps its size).  sm_create(out, p, dev) is
+ * sm_create_ex(out, p, NULL, dev); NULL means the defaults, under which every refusal and its text is sm_create's.
+ *   so_float_minima = 1: the scan-line optimisers (so, so_R2L, so_T2D) take every minimum as the reference's C++
+ *     loop does: m = c[0], i = 0; for d = 1 .. D-1: if (c[d] < m) { m = c[d]; i = d; } -- float compares, the first
+ *     index of equal values (-0 == +0), a NaN at index 0 sticky ((NaN, 0) whatever follows), a NaN elsewhere never
+ *     taken.  The forward step's compares are false when a side is NaN, so a NaN cost stays NaN along its line and
+ *     is never chosen over a number.  Defined for finite costs of either sign, +-0 and NaN.  Where an accumulated
+ *     cost kept with keep_final_volume is not NaN its bits are the reference's; NaN payloads and signs are not
+ *     pinned.  With a +inf cost the reference's own backtrack leaves its trace (FLT_MAX < +inf selects d - 1 at
+ *     d = 0 and d + 1 at d = D - 1); here the backtrack's disparity is clamped to [0, num_disparities), no access
+ *     leaves the line's own trace and every other line (row for so / so_R2L, column for so_T2D) is unaffected; what
+ *     the map holds on the affected line is unspecified.
+ *     sm_create's four refusals of "so" fall away: after GF, after GFNL, and after BF with a gradient cost method or
+ *     with ad_trunc_ad off the 2^-25 grid.  Every other check is unchanged.  After an aggregation whose costs are
+ *     >= +0 the option is allowed too and gives the same maps and volumes from the float-minima kernels.  On a
+ *     context whose optimization is not SM_OPT_SO it is accepted and changes nothing.
+ * SM_EINVAL, with the field named in sm_last_error, for a struct_size other than sizeof(sm_create_opts) and for
+ * so_float_minima outside {0, 1}: checked before sm_params and without a device. */
+typedef struct sm_create_opts {
+    uint32_t struct_size;        /* = sizeof(sm_create_opts), set by sm_create_opts_default */
+    int32_t so_float_minima;     /* 0 (default): as sm_create.  1: see above */
+} sm_create_opts;
+SM_API void sm_create_opts_default(sm_create_opts* o);
+SM_API sm_status sm_create_ex(sm_ctx** out, const sm_params* p, const sm_create_opts* opts, int32_t hip_device);
 SM_API sm_status sm_destroy(sm_ctx* ctx);
 SM_API const char* sm_last_error(const sm_ctx* ctx);
 SM_API const char* sm_status_string(sm_status s);
@@ -420,7 +448,8 @@ SM_API sm_status sm_gfnl_config(sm_ctx* ctx, float var_thresh);
  * Not sm_params fields (the struct keeps its size): SM_SO_L2R with 1.2 / 3.6 by default, takes effect from the next
  * sm_disp_optimize / sm_run; with a pyramid the call concerns level 0 only.  keep_final_volume: SM_SO_R2L leaves its
  * accumulated volume in vm[view], as so does.  The eval table's stage 0 keeps the name "so" (cpp:1102).  Every
- * refusal that exists with "so" holds for all variants.  The maps are the same for every schedule.  Profile names:
+ * refusal that exists with "so" holds for all variants, and so does what sm_create_ex's so_float_minima lifts (after
+ * GF, GFNL and inexact BF all three variants run, on their float-minima kernels).  The maps are the same for every schedule.  Profile names:
  * "so_r2l[_r]", "so_t2d[_r]".  SM_EINVAL, with the argument named in sm_last_error, for a variant outside [0, 2], a
  * penalty that is neither SM_SO_PN_DEFAULT nor finite and >= +0, or a context whose optimization is not SM_OPT_SO
  * (unless the call is the all-default one: SM_SO_L2R, SM_SO_PN_DEFAULT, SM_SO_PN_DEFAULT); the arguments are checked
@@ -513,7 +542,9 @@ typedef enum sm_se_mode {
  * pairs).  SM_EINVAL, with the argument named in sm_last_error, on a context without do_refine, for a pkr_ratio
  * that is not finite, disp_pkr outside [-32768, -1], bg_ipl_depth outside [0, 32767], se_mode outside {0, 1},
  * do_pkr with num_disparities < 2 (the reference's second search writes slot -1), and do_pkr or do_subpixel with
- * optimization "so" (the reference's so rewrites vm in place, cpp:6299; this back end keeps a trace instead);
+ * optimization "so" and keep_final_volume = 0 (the reference's so rewrites vm in place, cpp:6299; this back end keeps
+ * a trace instead).  With "so" and keep_final_volume = 1 the stages read vm[0] as the reference's refine() finds it:
+ * the accumulated volume after so and so_R2L, the volume after SolveAll after so_T2D (which runs on a clone);
  * the arguments are checked without a device.  Do_discontinuityAdjust is built (sm_refine_da_config).  Not built:
  * Do_WM (reads a mask the shipped LR check never writes; with sm_refine_outlier_config's classify the mask exists,
  * but the stage still indexes a histogram with negative disparities) and Do_cbbi (needs floodFill and theRNG()). */
@@ -542,7 +573,8 @@ SM_API sm_status sm_download_subpixel(sm_ctx* ctx, int32_t n, float* dst);
  * vm[0] for the stage to read, as for do_pkr; switched on after sm_disp_optimize ran without it, sm_refine returns
  * SM_ESTATE.  The maps are the same for every schedule; no launch count depends on the data and nothing is read
  * back.  The scratch is allocated on the first enabling call (batch_capacity pairs).  SM_EINVAL, with the argument
- * named in sm_last_error, on a context without do_refine, with optimization "so", for a threshold outside
+ * named in sm_last_error, on a context without do_refine, with optimization "so" and keep_final_volume = 0 (with 1
+ * the stage reads vm[0] as for do_pkr), for a threshold outside
  * [0, 32767] (given in the wrong order they are swapped), a negative tap or 2 * blur_side + blur_centre > 256; the
  * arguments are checked without a device. */
 SM_API sm_status sm_refine_da_config(sm_ctx* ctx, int32_t on, int32_t canny_low, int32_t canny_high, int32_t blur_side,

@@ -358,6 +358,10 @@ class StereoMatching {
     // as aggregated).  SO_PN2 / SO_PN3 replace the chosen function's literals (SM_SO_PN_DEFAULT keeps them)
     inline static int SO_VARIANT = SM_SO_L2R;
     inline static float SO_PN2 = SM_SO_PN_DEFAULT, SO_PN3 = SM_SO_PN_DEFAULT;
+    // the scan-line optimisers' float-minima kernels (sm_create_ex, so_float_minima): -1 = automatic, on where "so"
+    // follows GF, GFNL or BF over a gradient cost method (signed or NaN costs; the reference runs them without a
+    // switch); 0 / 1 force it
+    inline static int SO_FLOAT_MINIMA = -1;
     // the reference's err txt (saveFromDisp -> calErr after dispOptimize and after refine()'s stages; sm_eval_config):
     // with DT given, the table is built on the GPU while dispOptimize and refine() run; stageErrors() returns its rows
     inline static bool Do_stageErrors = false;
@@ -660,7 +664,21 @@ class StereoMatching {
         p.gf_mode = gf_my_guide ? SM_GF_MY_GUIDE : SM_GF_XIMGPROC;
         p.fif_mode = fif_plain ? SM_FIF_PLAIN : SM_FIF_IMPROVE;
         p.lr_consis = Do_LRConsis ? 1 : 0;
-        check(sm_create(&ctx_, &p, hip_device), "sm_create");
+        const bool so_on = optimization == "so";
+        // refine()'s volume-reading stages after "so" read vm[0] as so left it (the reference's so accumulates in place)
+        if (so_on && Do_refine && (Do_calPKR || Do_subpixelEnhancement || Do_discontinuityAdjust)) p.keep_final_volume = 1;
+        const bool bf_inexact = aggregation == "BF" && (p.cost_method == SM_COST_GRAD || p.cost_method == SM_COST_AD_GRAD ||
+                                                        p.cost_method == SM_COST_AD_CENSUS_GRAD);
+        const bool fm = SO_FLOAT_MINIMA >= 0 ? SO_FLOAT_MINIMA != 0
+                                             : so_on && (aggregation == "GF" || aggregation == "GFNL" || bf_inexact);
+        if (fm) {
+            sm_create_opts o;
+            sm_create_opts_default(&o);
+            o.so_float_minima = 1;
+            check(sm_create_ex(&ctx_, &p, &o, hip_device), "sm_create_ex");
+        } else {
+            check(sm_create(&ctx_, &p, hip_device), "sm_create");
+        }
         if (aggregation == "AWS") check(sm_aws_config(ctx_, aws_radius_v, aws_radius_u, aws_gamma_c), "sm_aws_config");
         if (aggregation == "BF") check(sm_bf_config(ctx_, bf_ksize_v, bf_ksize_u), "sm_bf_config");
         if (aggregation == "GFNL") check(sm_gfnl_config(ctx_, gfnl_var_thresh), "sm_gfnl_config");

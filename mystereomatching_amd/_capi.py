@@ -6,6 +6,7 @@ there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,6 +69,12 @@ class sm_params(C.Structure):
     ]
 
 
+class sm_create_opts(C.Structure):
+    """Mirror of struct sm_create_opts (include/sm_capi.h)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("so_float_minima", C.c_int32)]
+
+
 class sm_stage_err(C.Structure):
     """Mirror of struct sm_stage_err (include/sm_capi.h): one (pair, stage, region) of the error table."""
 
@@ -86,6 +93,8 @@ _u8p = C.POINTER(C.c_uint8)
 SIGNATURES = [
     ("sm_params_default", None, [C.POINTER(sm_params), C.c_int32, C.c_int32, C.c_int32]),
     ("sm_create", C.c_int, [C.POINTER(_P), C.POINTER(sm_params), C.c_int32]),
+    ("sm_create_opts_default", None, [C.POINTER(sm_create_opts)]),
+    ("sm_create_ex", C.c_int, [C.POINTER(_P), C.POINTER(sm_params), C.POINTER(sm_create_opts), C.c_int32]),
     ("sm_destroy", C.c_int, [_P]),
     ("sm_last_error", C.c_char_p, [_P]),
     ("sm_status_string", C.c_char_p, [C.c_int]),
@@ -212,6 +221,48 @@ def default_params(max_disp: int, rows: int, cols: int, **overrides) -> sm_param
             raise AttributeError(f"sm_params has no field {k!r}")
         setattr(p, k, v)
     return p
+
+
+def create_opts(so_float_minima: bool = False) -> sm_create_opts:
+    """What sm_create_opts_default fills in, then the fields given."""
+    o = sm_create_opts()
+    o.struct_size = C.sizeof(sm_create_opts)
+    o.so_float_minima = int(bool(so_float_minima))
+    return o
+
+
+# cost methods with a gradient term: BF's box sums over them are not exact (sm_validate.cpp, cost_has_grad_ext)
+_BF_INEXACT_COSTS = (COST_METHODS["grad"], COST_METHODS["adGrad"], COST_METHODS["ADCensusGrad"])
+
+
+def so_needs_float_minima(p: sm_params) -> bool:
+    """The combinations sm_create refuses and sm_create_ex with so_float_minima = 1 runs: optimization "so" after GF or
+    GFNL, or after BF with inexact sums (a gradient cost method, or AD / SD with ad_trunc_ad off the 2^-25 grid or
+    above 1024: bf_exact in sm_validate.cpp).  The reference runs them without a switch, so the facades take this
+    for their automatic setting."""
+    if p.optimization != OPTIMIZATIONS["so"]:
+        return False
+    if p.aggregation in (AGGREGATIONS["GF"], AGGREGATIONS["GFNL"]):
+        return True
+    if p.aggregation != AGGREGATIONS["BF"]:
+        return False
+    if p.cost_method in _BF_INEXACT_COSTS:
+        return True
+    if p.cost_method not in (COST_METHODS["AD"], COST_METHODS["SD"]):
+        return False
+    t = float(p.ad_trunc_ad)
+    return not (t <= 1024.0 and math.ldexp(t, 25) == math.floor(math.ldexp(t, 25)))
+
+
+def create(lib, p: sm_params, device: int, so_float_minima=None):
+    """sm_create, or sm_create_ex where the float-minima optimisers are asked for (True), or needed and not refused
+    (None: automatic).  Returns (ctx, status, the entry point's name)."""
+    ctx = C.c_void_p()
+    fm = so_needs_float_minima(p) if so_float_minima is None else bool(so_float_minima)
+    if not fm:
+        return ctx, lib.sm_create(C.byref(ctx), C.byref(p), device), "sm_create"
+    o = create_opts(so_float_minima=True)
+    return ctx, lib.sm_create_ex(C.byref(ctx), C.byref(p), C.byref(o), device), "sm_create_ex"
 
 
 def ptr(a):

@@ -79,7 +79,9 @@ def pinned_batch(n: int, H: int, W: int) -> dict:
 
 def hip_compute_fn(max_disp: int, rows: int, cols: int, capacity: int, device: int, **overrides) -> Callable:
     """The product compute path: a StereoBatch on this rank's GPU.  `overrides` are StereoBatch's: sm_params
-    fields and the feature settings beside them (py_lvl=L runs the cross-scale pyramid in every block)."""
+    fields and the feature settings beside them (py_lvl=L runs the cross-scale pyramid in every block;
+    so_float_minima=True|False|None chooses the scan-line optimisers' float-minima kernels, None automatically where
+    "so" follows GF, GFNL or BF with inexact sums)."""
     from .stereo_matching import StereoBatch, _is_device_tensor
 
     sb = StereoBatch(max_disp, rows, cols, capacity, device=device, **overrides)

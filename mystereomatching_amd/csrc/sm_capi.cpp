@@ -103,7 +103,7 @@ void free_all(sm_ctx* c) {
 
 // sm_create; with `owner`, pyramid level `level` of that context (sm_pyramid_config), which needs no map or
 // refine planes beyond DP[0]'s
-static sm_status create_ctx(sm_ctx** out, const sm_params* p, int32_t hip_device, sm_ctx* owner, int level) {
+static sm_status create_ctx(sm_ctx** out, const sm_params* p, const sm_create_opts* opts, int32_t hip_device, sm_ctx* owner, int level) {
     if (!out || !p) return SM_EINVAL;
     *out = nullptr;
     sm_ctx* c = new (std::nothrow) sm_ctx();
@@ -111,6 +111,15 @@ static sm_status create_ctx(sm_ctx** out, const sm_params* p, int32_t hip_device
     *out = c;  // returned even on failure so sm_last_error works; caller must sm_destroy
     c->owner = owner;
     c->level = level;
+    // the options first (NULL: the defaults), before any field of sm_params is read
+    if (opts) {
+        if (opts->struct_size != (uint32_t)sizeof(sm_create_opts))
+            return fail(c, SM_EINVAL, "sm_create_opts.struct_size != sizeof(sm_create_opts): initialise the struct with "
+                                      "sm_create_opts_default from this library's sm_capi.h");
+        if (opts->so_float_minima != 0 && opts->so_float_minima != 1)
+            return fail(c, SM_EINVAL, "sm_create_opts.so_float_minima must be 0 or 1");
+        c->so_float_minima = opts->so_float_minima == 1;
+    }
     // a struct from another version of sm_capi.h (or not filled by sm_params_default) is refused
     // before any field past struct_size is read
     if (p->struct_size != (uint32_t)sizeof(sm_params))
@@ -121,7 +130,7 @@ static sm_status create_ctx(sm_ctx** out, const sm_params* p, int32_t hip_device
     if (hipDeviceGetAttribute(&c->num_cu, hipDeviceAttributeMultiprocessorCount, hip_device) != hipSuccess || c->num_cu < 1)
         c->num_cu = 256;
     std::string why;
-    if (validate(c->p, why) != SM_OK) return fail(c, SM_EINVAL, why);
+    if (validate(c->p, why, c->so_float_minima) != SM_OK) return fail(c, SM_EINVAL, why);
     int ndev = 0;
     HIP_TRY(c, hipGetDeviceCount(&ndev));
     if (hip_device < 0 || hip_device >= ndev) return fail(c, SM_EINVAL, "hip_device out of range");
@@ -282,7 +291,11 @@ static void destroy_levels(sm_ctx* c) {
 
 extern "C" {
 
-sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) { return create_ctx(out, p, hip_device, nullptr, 0); }
+sm_status sm_create(sm_ctx** out, const sm_params* p, int32_t hip_device) { return sm_create_ex(out, p, nullptr, hip_device); }
+
+sm_status sm_create_ex(sm_ctx** out, const sm_params* p, const sm_create_opts* opts, int32_t hip_device) {
+    return create_ctx(out, p, opts, hip_device, nullptr, 0);
+}
 
 sm_status sm_destroy(sm_ctx* c) {
     if (!c) return SM_OK;
@@ -958,7 +971,9 @@ sm_status sm_refine_ext_config(sm_ctx* c, int32_t do_pkr, float pkr_ratio, int32
         return fail(c, SM_EINVAL, "se_mode must be SM_SE_REFERENCE (0) or SM_SE_FLOAT (1)");
     if (do_pkr && c->p.num_disparities < 2)
         return fail(c, SM_EINVAL, "do_pkr needs num_disparities >= 2 (calPKR's second search is undefined with one cost)");
-    if ((do_pkr || do_subpixel) && c->p.optimization == SM_OPT_SO)
+    // with keep_final_volume k_so leaves the reference's accumulated volume in vm[0] (so_T2D runs on a clone there
+    // and leaves the volume after SolveAll): what the reference's refine() reads
+    if ((do_pkr || do_subpixel) && c->p.optimization == SM_OPT_SO && !c->p.keep_final_volume)
         return fail(c, SM_EINVAL, do_pkr ? "do_pkr: not with optimization so (the reference's so rewrites vm[0] in place)"
                                          : "do_subpixel: not with optimization so (the reference's so rewrites vm[0] in place)");
     if (c->st) {   // a live context
@@ -1027,7 +1042,7 @@ sm_status sm_refine_da_config(sm_ctx* c, int32_t on, int32_t canny_low, int32_t 
     if (sm_status r = refuse_level(c)) return r;
     // the arguments are checked before any device call, so on a machine without a GPU too
     if (!c->p.do_refine) return fail(c, SM_EINVAL, "sm_refine_da_config: the context has do_refine = 0 (refine() never runs)");
-    if (c->p.optimization == SM_OPT_SO)
+    if (c->p.optimization == SM_OPT_SO && !c->p.keep_final_volume)   // (with it: see sm_refine_ext_config)
         return fail(c, SM_EINVAL, "sm_refine_da_config: not with optimization so (the reference's so rewrites vm[0] in place)");
     if (canny_low < 0 || canny_low > 32767) return fail(c, SM_EINVAL, "canny_low must be in [0, 32767]");
     if (canny_high < 0 || canny_high > 32767) return fail(c, SM_EINVAL, "canny_high must be in [0, 32767]");
@@ -1259,7 +1274,7 @@ sm_status sm_pyramid_config(sm_ctx* c, int32_t py_lvl) {
     for (int l = 1; l < py_lvl; l++) {
         lp.push_back(level_params(c->p, lp[l - 1], l));
         std::string why;
-        if (validate(lp[l], why) == SM_OK && lp[l].aggregation == SM_AGG_BF &&
+        if (validate(lp[l], why, c->so_float_minima) == SM_OK && lp[l].aggregation == SM_AGG_BF &&
             (lp[l].rows < c->bf_kv / 2 + 1 || lp[l].cols < c->bf_ku / 2 + 1))
             why = "aggregation BF: the window (sm_bf_config) does not fit the image";
         if (!why.empty())
@@ -1277,7 +1292,10 @@ sm_status sm_pyramid_config(sm_ctx* c, int32_t py_lvl) {
     }
     for (int l = 1; l < py_lvl && !s; l++) {
         sm_ctx* q = nullptr;
-        s = create_ctx(&q, &lp[l], c->device, c, l);
+        sm_create_opts lo;   // a level is created under its owner's options
+        sm_create_opts_default(&lo);
+        lo.so_float_minima = c->so_float_minima;
+        s = create_ctx(&q, &lp[l], &lo, c->device, c, l);
         if (q) c->levels.push_back(q);
         // the owner's aggregation-side settings (the *_config calls made before this one)
         if (!s && c->p.aggregation == SM_AGG_AWS) s = aws_config_one(q, c->aws_rv, c->aws_ru, c->aws_gamma, false);

@@ -61,6 +61,7 @@ struct sm_ctx {
     // which scan-line optimiser dispOptimize runs (sm_so_config; the call commented in at cpp:1096-1100)
     int so_variant = SM_SO_L2R;
     float so_pn2 = 1.2f, so_pn3 = 3.6f;   // the chosen function's Pn2 / Pn3 (so cpp:6305-6306)
+    bool so_float_minima = false;         // sm_create_opts::so_float_minima: the optimisers' FM kernels (signed / NaN costs)
     uint32_t* px = nullptr;     // [cap][2][npix] packed BGR, then the pxh and pxv arm-walk planes (same shape)
     // aggregation "GF": three scratch volumes (the SGM sum is the fourth), image planes, per-pixel terms
     float* gf_s = nullptr;      // [3 (+1 without acc)][cap][nvol]
@@ -484,7 +485,8 @@ bool refine_reads_volume(const sm_ctx* c);
 const char* outlier_config_error(const sm_params& p, int classify, int disp_mis, int rv_combine, int interpolate_type);
 int dw_int_threshold(float thres);
 bool cbca_div_safe(const sm_params& p, int k);
-sm_status validate(const sm_params& p, std::string& why);
+// so_float_minima (sm_create_opts): "so" is then allowed after GF, GFNL and BF with inexact sums
+sm_status validate(const sm_params& p, std::string& why, bool so_float_minima = false);
 void build_luts(sm_ctx* c);
 
 // sm_stages.cpp (all asynchronous on the group's stream)

@@ -271,6 +271,7 @@ struct SoArgs {                 // scan-line optimisation "so" (sm_so.hip)
     int H, W, D, n, keep_final;
     int r2l;                    // 0: so (left to right); 1: so_R2L (right to left).  launch_so only
     float pn2, pn3;             // the functions' Pn2 / Pn3 literals (so 1.2 / 3.6; so_R2L, so_T2D 0.3 / 0.9)
+    int float_minima;           // 1: the FM instantiations (minima as the reference's C++ takes them: signed and NaN costs)
 };
 
 constexpr int kMaxPyr = 8;      // PY_LVL limit (sm_solve_all_pyr)

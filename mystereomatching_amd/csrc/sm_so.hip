@@ -11,7 +11,8 @@
 //
 // gfx950 mapping: one wave per (pair, row), lane l owns K consecutive disparities (registers);
 // the row minimum is an unsigned-integer DPP reduction (every cost is >= +0, so bit patterns
-// order like the floats) plus a ballot for the first index; d +- 1 across lane edges come by DPP
+// order like the floats; the FM instantiation, below, takes costs of either sign and NaN) plus a ballot for the
+// first index; d +- 1 across lane edges come by DPP
 // wave shifts.  Columns are prefetched a tile ahead.  The trace is stored as one byte per element
 // (0: d, 1: d - 1, 2: d + 1, 3: the row minimum's index, kept per column), so the backtrack — a
 // chain of W dependent reads, inherently sequential — reads one byte and one u16 per column.
@@ -45,7 +46,15 @@ __device__ __forceinline__ int so_col(int W, int s) {   // the column of step s 
     return R2L ? W - 1 - s : s;
 }
 
-template <int K, bool LT, bool R2L>
+//
+// FM (float minima; sm_create_opts::so_float_minima): every minimum is so_first_min (sm_so_step.h), the reference's
+// own float loop, so the costs may have either sign and be NaN (GF, GFNL, inexact BF).  so_step needs nothing: each
+// of its `<` is false when a side is NaN, so a NaN prev[d] gives cost_min = NaN, code 0 and nv = NaN, and a NaN
+// c_min is never taken.  Padding lanes are skipped by so_first_min and never read as a neighbour (so_step's d > 0 /
+// d < D - 1 guards).  With a +inf cost the reference's `FLT_MAX < +inf` selects d - 1 at d = 0 (d + 1 at d = D - 1)
+// and its backtrack leaves the trace; here the backtrack's disparity is clamped to [0, D), so every access stays
+// inside the line's own trace.  What the map holds on such a line is unspecified; other lines are independent.
+template <int K, bool LT, bool R2L, bool FM>
 __global__ __launch_bounds__(256) void k_so(const SoArgs a) {
     extern __shared__ __align__(16) uint64_t so_lds[];
     const int lane = threadIdx.x & 63;
@@ -107,12 +116,18 @@ __global__ __launch_bounds__(256) void k_so(const SoArgs a) {
                     lm = prev[j];
                     li = d0 + j;
                 }
-            const uint32_t wm = wave_umin(__builtin_bit_cast(uint32_t, lm));
-            const uint64_t hit = __ballot(__builtin_bit_cast(uint32_t, lm) == wm);
-            const int cidx = __builtin_amdgcn_readlane(li, (int)__builtin_ctzll(hit));
+            float wmin;
+            int cidx;
+            if (FM) {
+                cidx = so_first_min<K>(prev, d0, D, wmin);
+            } else {
+                const uint32_t wm = wave_umin(__builtin_bit_cast(uint32_t, lm));
+                const uint64_t hit = __ballot(__builtin_bit_cast(uint32_t, lm) == wm);
+                cidx = __builtin_amdgcn_readlane(li, (int)__builtin_ctzll(hit));
+                wmin = __builtin_bit_cast(float, wm);
+            }
             float nv[K];
-            so_step<K, false, LT>(prev, t[k], nv, __builtin_bit_cast(float, wm), Pn2, Pn3, d0, D, lane, tl + (size_t)u * 2 * K,
-                                  trow + (size_t)u * D);
+            so_step<K, false, LT>(prev, t[k], nv, wmin, Pn2, Pn3, d0, D, lane, tl + (size_t)u * 2 * K, trow + (size_t)u * D);
             if (lane == 0) {
                 if (LT)
                     cl[u] = (uint16_t)cidx;
@@ -146,9 +161,14 @@ __global__ __launch_bounds__(256) void k_so(const SoArgs a) {
                 lm = prev[j];
                 li = d0 + j;
             }
-        const uint32_t wm = wave_umin(__builtin_bit_cast(uint32_t, lm));
-        const uint64_t hit = __ballot(__builtin_bit_cast(uint32_t, lm) == wm);
-        dmin = __builtin_amdgcn_readlane(li, (int)__builtin_ctzll(hit));
+        if (FM) {
+            float wmin;
+            dmin = so_first_min<K>(prev, d0, D, wmin);
+        } else {
+            const uint32_t wm = wave_umin(__builtin_bit_cast(uint32_t, lm));
+            const uint64_t hit = __ballot(__builtin_bit_cast(uint32_t, lm) == wm);
+            dmin = __builtin_amdgcn_readlane(li, (int)__builtin_ctzll(hit));
+        }
     }
     __threadfence_block();   // this wave's trace stores are visible to its own loads
     int16_t* drow = a.disp + pix0;
@@ -157,6 +177,7 @@ __global__ __launch_bounds__(256) void k_so(const SoArgs a) {
     outv = lane == (so_col<R2L>(W, u) & 63) ? dmin : outv;
     for (; u > 0; u--) {
         dmin = so_trace_next<K, LT>(dmin, tl + (size_t)u * 2 * K, trow + (size_t)u * D, LT ? cl[u] : crow[u]);
+        if (FM) dmin = min(max(dmin, 0), D - 1);   // a +inf cost's trace may point outside [0, D) (see above)
         const int t = so_col<R2L>(W, u - 1);
         if (R2L) {   // columns rise: group t - 64 .. t - 1 is complete when column t opens the next one
             if ((t & 63) == 0) {
@@ -187,15 +208,20 @@ void launch_so(const SoArgs& a, hipStream_t st) {
     const size_t shm = 4 * so_lds_words(a.W, kk) * 8;
     const bool lt = shm <= 64 * 1024;   // the row's trace in LDS when it fits, else in global memory
     const size_t sh = lt ? shm : 0;
-#define SM_SO_LAUNCH(KV)                                                                       \
-    do {                                                                                       \
-        if (a.r2l) {                                                                           \
-            if (lt) hipLaunchKernelGGL((k_so<KV, true, true>), grid, dim3(256), sh, st, a);    \
-            else hipLaunchKernelGGL((k_so<KV, false, true>), grid, dim3(256), 0, st, a);       \
-        } else {                                                                               \
-            if (lt) hipLaunchKernelGGL((k_so<KV, true, false>), grid, dim3(256), sh, st, a);   \
-            else hipLaunchKernelGGL((k_so<KV, false, false>), grid, dim3(256), 0, st, a);      \
-        }                                                                                      \
+#define SM_SO_LAUNCH_FM(KV, FMV)                                                                    \
+    do {                                                                                            \
+        if (a.r2l) {                                                                                \
+            if (lt) hipLaunchKernelGGL((k_so<KV, true, true, FMV>), grid, dim3(256), sh, st, a);    \
+            else hipLaunchKernelGGL((k_so<KV, false, true, FMV>), grid, dim3(256), 0, st, a);       \
+        } else {                                                                                    \
+            if (lt) hipLaunchKernelGGL((k_so<KV, true, false, FMV>), grid, dim3(256), sh, st, a);   \
+            else hipLaunchKernelGGL((k_so<KV, false, false, FMV>), grid, dim3(256), 0, st, a);      \
+        }                                                                                           \
+    } while (0)
+#define SM_SO_LAUNCH(KV)                                 \
+    do {                                                 \
+        if (a.float_minima) SM_SO_LAUNCH_FM(KV, true);   \
+        else SM_SO_LAUNCH_FM(KV, false);                 \
     } while (0)
     if (kk == 1) SM_SO_LAUNCH(1);
     else if (kk == 2) SM_SO_LAUNCH(2);
@@ -203,6 +229,7 @@ void launch_so(const SoArgs& a, hipStream_t st) {
     else if (kk == 8) SM_SO_LAUNCH(8);
     else SM_SO_LAUNCH(16);
 #undef SM_SO_LAUNCH
+#undef SM_SO_LAUNCH_FM
 }
 
 }  // namespace sm

@@ -1,8 +1,9 @@
 // sm_so_step.h — what the scan-line optimiser kernels share (k_so in sm_so.hip: so and so_R2L; k_so_t2d in
 // sm_so_t2d.hip: so_T2D): one step of the dynamic programme for a lane's K consecutive disparities, the two trace
 // stores and the trace read of the backtrack.  The kernels differ in the scan (rows or columns, its direction and
-// strides), in the minimum they hand in (bit patterns for costs >= +0, floats for so_T2D's signed costs) and in the
-// addend (cost_min, or so_T2D's cost_min - c_min).
+// strides), in the minimum they hand in (bit patterns for costs >= +0, floats for so_T2D's signed costs, or
+// so_first_min below: the reference's own loop, for costs of either sign and NaN) and in the addend (cost_min, or
+// so_T2D's cost_min - c_min).
 #pragma once
 #include <float.h>
 #include <hip/hip_runtime.h>
@@ -26,6 +27,44 @@ __device__ __forceinline__ float so_shr1_f(float v) {   // lane l <- lane l - 1 
 __device__ __forceinline__ float so_shl1_f(float v) {   // lane l <- lane l + 1 (lane 63 <- FLT_MAX)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp((int)0x7f7fffff, __builtin_bit_cast(int, v),
                                                                  DPP_WAVE_SHL1, 0xF, 0xF, false));
+}
+
+// The reference's first minimum of a line's D costs, as its C++ takes it (cpp:6354-6363, 6396-6406):
+//   m = c[0], i = 0;  for d = 1 .. D-1: if (c[d] < m) { m = c[d]; i = d; }
+// for costs of either sign, +-0 and NaN: -0 == +0 (the first of equal values wins whatever its sign bit), a NaN at
+// index 0 is sticky (every later compare is false: the result is (NaN, 0)), a NaN at any other index never wins.
+// Lane l holds p = c[d0 .. d0 + K); disparities >= D (padding) never win, whatever the real costs are.  Returns i and
+// sets wm = m (wave-uniform: c[i] itself, read from the lane that holds it).
+// In the lane, the loop's own compares, skipping NaN (a NaN running value is replaced by whatever follows, so it
+// stays NaN only while every value was).  Across lanes, an unsigned minimum of one order-preserving key per lane:
+// floats map to keys monotonically (-0 first folded onto +0, so the two zeros share a key and the lower lane wins
+// the tie), NaN and padding to the largest key, the sticky NaN of lane 0 to key 0, below -inf's.  The integer
+// minimum always equals some lane's key, so the ballot is never empty; v_min_f32, which drops NaN and may return
+// either zero, is not used.  (If every key is the largest, c[0] is NaN and held key 0: impossible.)
+template <int K>
+__device__ __forceinline__ int so_first_min(const float (&p)[K], int d0, int D, float& wm) {
+    float lm = p[0];
+    int li = d0;
+#pragma unroll
+    for (int j = 1; j < K; j++) {
+        const bool take = d0 + j < D && (p[j] < lm || lm != lm);
+        lm = take ? p[j] : lm;
+        li = take ? d0 + j : li;
+    }
+    const bool sticky = d0 == 0 && p[0] != p[0];
+    if (sticky) {
+        lm = p[0];
+        li = 0;
+    }
+    uint32_t b = __builtin_bit_cast(uint32_t, lm);
+    b = (b << 1) == 0 ? 0u : b;                                           // -0 -> +0
+    uint32_t key = b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);      // negative: all bits flipped; else the sign bit set
+    if (lm != lm || d0 >= D) key = 0xffffffffu;
+    if (sticky) key = 0u;
+    const uint32_t km = wave_umin(key);
+    const int src = (int)__builtin_ctzll(__ballot(key == km));
+    wm = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lm), src));
+    return __builtin_amdgcn_readlane(li, src);
 }
 
 // L_isDisc of two packed BGR pixels: float sum = 0; sum += abs(IP[c] - IP_pre[c]); sum /= 3; sum > 15 (cpp:6285-6296)

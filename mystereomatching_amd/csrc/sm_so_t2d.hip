@@ -12,7 +12,8 @@
 //   trace(v, u)[d] = the chosen disparity
 // The addend is <= 0, so the accumulated costs go negative even on costs >= +0: every minimum here is a float
 // minimum (v_min_f32 and float compares: -0 == +0, first index on ties), never one on bit patterns.  Costs are
-// finite, as for so: lanes past D hold FLT_MAX and never win against a real cost, and no NaN is ordered.
+// finite, as for so: lanes past D hold FLT_MAX and never win against a real cost, and no NaN is ordered (the FM
+// instantiation, below, takes NaN too).
 // The last-row minimum is `if (c_min > vP[d])` (cpp:6659, first index); the backtrack follows
 // trace(v, u)[disp(v, u)] upwards (cpp:6667-6679).  The reference's backtrack sits inside its column loop; its last
 // execution, after every column's forward pass, is the result, and that is what this kernel computes.
@@ -55,14 +56,17 @@ __device__ __forceinline__ int t2d_argmin(const float (&p)[K], int d0, float& wm
         }
     // v_min_f32 may return either zero when -0 meets +0, per lane; one lane's value is taken for all.
     // Finite costs are a precondition the ballot depends on: a NaN minimum equals no lane's value, hit would be 0 and
-    // the lane index 64 (k_so's compare of bit patterns always has a hit).  sm_create keeps it: it refuses "so" after
-    // the aggregations whose costs may be signed or NaN (GF, GFNL, inexact BF), and sm_so_config needs "so".
+    // the lane index 64 (k_so's compare of bit patterns always has a hit).  A default sm_create keeps it: it refuses
+    // "so" after the aggregations whose costs may be signed or NaN (GF, GFNL, inexact BF).  Contexts created with
+    // so_float_minima = 1 lift those refusals and run the FM instantiation below, which never comes here.
     wm = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_min(lm))));
     const uint64_t hit = __ballot(lm == wm);
     return __builtin_amdgcn_readlane(li, (int)__builtin_ctzll(hit));
 }
 
-template <int K, bool LT>
+// FM (float minima; sm_create_opts::so_float_minima): every minimum is so_first_min (sm_so_step.h), defined for NaN
+// too, and the backtrack's disparity is clamped to [0, D) as in k_so (a +inf cost; the column's map is unspecified).
+template <int K, bool LT, bool FM>
 __global__ __launch_bounds__(256) void k_so_t2d(const SoArgs a) {
     extern __shared__ __align__(16) uint64_t t2d_lds[];
     const int lane = threadIdx.x & 63;
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(256) void k_so_t2d(const SoArgs a) {
             // addresses and keeps the whole closure in scratch memory)
             const float Pn2 = dc ? a.pn2 / 2 : a.pn2, Pn3 = dc ? a.pn3 / 2 : a.pn3;   // Pn /= 2 on a discontinuity
             float wm;
-            const int cidx = t2d_argmin<K>(prev, d0, wm);
+            const int cidx = FM ? so_first_min<K>(prev, d0, D, wm) : t2d_argmin<K>(prev, d0, wm);
             float nv[K];
             so_step<K, true, LT>(prev, t[k], nv, wm, Pn2, Pn3, d0, D, lane, tl + (size_t)v * 2 * K, tcol + (size_t)v * D);
             if (lane == 0) {
@@ -140,7 +144,7 @@ __global__ __launch_bounds__(256) void k_so_t2d(const SoArgs a) {
     }
     // backtrack: first minimum of the last row, then one trace read per row
     float wm;
-    int dmin = t2d_argmin<K>(prev, d0, wm);
+    int dmin = FM ? so_first_min<K>(prev, d0, D, wm) : t2d_argmin<K>(prev, d0, wm);
     __threadfence_block();   // this wave's trace stores are visible to its own loads
     int16_t* dcol = a.disp + (size_t)b * npix + u;   // row v at v * W
     int outv = 0;            // lane (v & 63) of the current 64-row group holds disp(v, u)
@@ -148,6 +152,7 @@ __global__ __launch_bounds__(256) void k_so_t2d(const SoArgs a) {
     outv = lane == (v & 63) ? dmin : outv;
     for (; v > 0; v--) {
         dmin = so_trace_next<K, LT>(dmin, tl + (size_t)v * 2 * K, tcol + (size_t)v * D, LT ? cl[v] : ccol[v]);
+        if (FM) dmin = min(max(dmin, 0), D - 1);
         const int t = v - 1;
         if ((t & 63) == 63) {   // the group of rows t + 1 .. has been filled: flush it
             const int g = t + 1;
@@ -167,10 +172,15 @@ void launch_so_t2d(const SoArgs& a, hipStream_t st) {
     const int kk = k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : (k <= 8 ? 8 : 16)));
     const size_t shm = 4 * so_lds_words(a.H, kk) * 8;
     const bool lt = shm <= 64 * 1024;   // the columns' traces in LDS when they fit, else in global memory
-#define SM_T2D_LAUNCH(KV)                                                                \
-    do {                                                                                 \
-        if (lt) hipLaunchKernelGGL((k_so_t2d<KV, true>), grid, dim3(256), shm, st, a);   \
-        else hipLaunchKernelGGL((k_so_t2d<KV, false>), grid, dim3(256), 0, st, a);       \
+#define SM_T2D_LAUNCH_FM(KV, FMV)                                                             \
+    do {                                                                                      \
+        if (lt) hipLaunchKernelGGL((k_so_t2d<KV, true, FMV>), grid, dim3(256), shm, st, a);   \
+        else hipLaunchKernelGGL((k_so_t2d<KV, false, FMV>), grid, dim3(256), 0, st, a);       \
+    } while (0)
+#define SM_T2D_LAUNCH(KV)                                 \
+    do {                                                  \
+        if (a.float_minima) SM_T2D_LAUNCH_FM(KV, true);   \
+        else SM_T2D_LAUNCH_FM(KV, false);                 \
     } while (0)
     if (kk == 1) SM_T2D_LAUNCH(1);
     else if (kk == 2) SM_T2D_LAUNCH(2);
@@ -178,6 +188,7 @@ void launch_so_t2d(const SoArgs& a, hipStream_t st) {
     else if (kk == 8) SM_T2D_LAUNCH(8);
     else SM_T2D_LAUNCH(16);
 #undef SM_T2D_LAUNCH
+#undef SM_T2D_LAUNCH_FM
 }
 
 }  // namespace sm

@@ -448,6 +448,7 @@ sm_status run_optimize(sm_ctx* c, int view, const Group& G) {
         a.keep_final = p.keep_final_volume;
         a.pn2 = c->so_pn2;
         a.pn3 = c->so_pn3;
+        a.float_minima = c->so_float_minima;
         // the call commented in at cpp:1096-1100 (sm_so_config)
         if (c->so_variant == SM_SO_T2D) {
             // so_T2D(vm_res, ..) runs on a clone (cpp:1095, 1097): vm[i] is read (4 B per element), never written

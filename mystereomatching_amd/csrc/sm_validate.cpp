@@ -125,7 +125,10 @@ bool cbca_div_safe(const sm_params& p, int k) {
 
 static bool nonneg(float x) { return x >= 0 && !std::signbit(x); }   // >= +0 (rejects NaN and -0.0)
 
-sm_status validate(const sm_params& p, std::string& why) {
+// so_float_minima (sm_create_opts): the scan-line optimisers then take float minima, defined for signed and NaN
+// costs, so the four refusals of "so" after GF, GFNL and inexact BF fall away; nothing else changes
+sm_status validate(const sm_params& p, std::string& why, bool so_float_minima) {
+    const bool so_unsigned = p.optimization == SM_OPT_SO && !so_float_minima;   // k_so's minima on bit patterns
     auto bad = [&](const char* m) { why = m; return SM_EINVAL; };
     if (p.rows < 2 || p.cols < 2) return bad("rows and cols must be >= 2 (calGrad reads I[1] and I[w-2])");
     if ((long long)p.rows * p.cols > (1LL << 30)) return bad("rows*cols too large");
@@ -138,12 +141,12 @@ sm_status validate(const sm_params& p, std::string& why) {
     if (p.aggregation == SM_AGG_BF) {
         // the default 12 x 12 window (anchor 6) with one REFLECT_101 reflection
         if (p.rows < 7 || p.cols < 7) return bad("aggregation BF needs rows, cols >= 7 (12 x 12 box, reflected border)");
-        if (p.optimization == SM_OPT_SO && cost_has_grad_ext(p)) {
+        if (so_unsigned && cost_has_grad_ext(p)) {
             const std::string msg = std::string("aggregation BF with optimization so is not supported for cost_method ") + cost_name(p.cost_method) +
                   " (its box sums are not exact, so a filtered cost may be -0)";
             return bad(msg.c_str());
         }
-        if (p.optimization == SM_OPT_SO && !bf_exact(p))
+        if (so_unsigned && !bf_exact(p))
             return bad("aggregation BF with optimization so needs ad_trunc_ad a multiple of 2^-25 and <= 1024 (exact sums)");
     }
     if (p.aggregation == SM_AGG_GFNL) {
@@ -153,7 +156,7 @@ sm_status validate(const sm_params& p, std::string& why) {
             return bad("aggregation GFNL (MY_GUIDE) needs rows, cols >= 19 (box radius 9)");
         // the variance plane's 19 x 19 box with REFLECT_101 (one reflection); covers GF's >= 9 and NL's >= 3
         if (p.rows < 10 || p.cols < 10) return bad("aggregation GFNL needs rows, cols >= 10 (19 x 19 variance box, reflected border)");
-        if (p.optimization == SM_OPT_SO) return bad("aggregation GFNL (costs may be negative) supports optimization sgm or WTA");
+        if (so_unsigned) return bad("aggregation GFNL (costs may be negative) supports optimization sgm or WTA");
         if (!(p.gf_eps > 0)) return bad("aggregation GFNL: gf_eps must be > 0");
         if (!(p.nl_sigma > 0)) return bad("aggregation GFNL: nl_sigma must be > 0");
         if (4.0 * (double)p.rows * (double)p.cols * (double)(p.batch_capacity > 0 ? p.batch_capacity : 1) >= 2147483647.0)
@@ -181,7 +184,7 @@ sm_status validate(const sm_params& p, std::string& why) {
         if (p.gf_mode == SM_GF_XIMGPROC && (p.rows < 9 || p.cols < 9))
             return bad("aggregation GF (ximgproc) needs rows, cols >= 9 (box radius 9, reflected border)");
         // the "so" optimiser's minima assume costs >= 0
-        if (p.optimization == SM_OPT_SO) return bad("aggregation GF (costs may be negative) supports optimization sgm or WTA");
+        if (so_unsigned) return bad("aggregation GF (costs may be negative) supports optimization sgm or WTA");
         if (!(p.gf_eps > 0)) return bad("gf_eps must be > 0");
     }
     if (p.aggregation == SM_AGG_NL) {
@@ -251,6 +254,13 @@ void build_luts(sm_ctx* c) {
 }
 
 extern "C" {
+
+void sm_create_opts_default(sm_create_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->struct_size = (uint32_t)sizeof(sm_create_opts);
+    o->so_float_minima = 0;
+}
 
 void sm_params_default(sm_params* p, int32_t max_disp, int32_t rows, int32_t cols) {
     if (!p) return;

@@ -182,8 +182,12 @@ class StereoMatching:
 
     def __init__(self, I1_c, I2_c, I1_g, I2_g, DT=None, all_mask=None, nonocc_mask=None, disc_mask=None,
                  param: Optional["StereoMatching.Parameters"] = None, device: int = 0,
-                 keep_final_volume: bool = False):
-        """StereoMatching::StereoMatching (cpp:2058-2110).  Images: BGR u8 HxWx3, gray u8 HxW."""
+                 keep_final_volume: bool = False, so_float_minima: Optional[bool] = None):
+        """StereoMatching::StereoMatching (cpp:2058-2110).  Images: BGR u8 HxWx3, gray u8 HxW.
+
+        so_float_minima: the scan-line optimisers' float-minima kernels (sm_create_ex).  None (default) is automatic:
+        on where optimization "so" follows GF, GFNL or BF with inexact sums, which the reference runs without a
+        switch; True / False force it."""
         I1_c, I2_c = np.ascontiguousarray(I1_c, np.uint8), np.ascontiguousarray(I2_c, np.uint8)
         I1_g, I2_g = np.ascontiguousarray(I1_g, np.uint8), np.ascontiguousarray(I2_g, np.uint8)
         h, w = I1_c.shape[:2]
@@ -208,12 +212,16 @@ class StereoMatching:
                        keep_final_volume=keep_final_volume, do_refine=self.Do_refine, lr_consis=self.Do_LRConsis,
                        switches=(self.Do_regionVote, self.Do_properIpol, self.Do_lastMedianBlur))
         self._refine_on = bool(self.Do_refine)
+        # refine()'s volume-reading stages after "so" read vm[0] as so left it (the reference's so accumulates in
+        # place): the context keeps it
+        if self.optimization == "so" and self._refine_on and (self.Do_calPKR or self.Do_subpixelEnhancement or
+                                                                self.Do_discontinuityAdjust):
+            p.keep_final_volume = 1
         self._so_views2 = self.optimization == "so" and bool(self.Do_LRConsis)   # as passed to sm_create
         p.rows, p.cols = h, w
-        ctx = C.c_void_p()
-        st = self._lib.sm_create(C.byref(ctx), C.byref(p), device)
+        ctx, st, entry = _capi.create(self._lib, p, device, so_float_minima)
         self._ctx = ctx
-        _capi.check(self._lib, ctx, st, "sm_create")
+        _capi.check(self._lib, ctx, st, entry)
         if self.aggregation == "AWS":
             st = self._lib.sm_aws_config(ctx, int(self.AWS_RADIUS_V), int(self.AWS_RADIUS_U), float(self.AWS_GAMMA_C))
             _capi.check(self._lib, ctx, st, "sm_aws_config")
@@ -455,13 +463,20 @@ class StereoBatch:
             raise ValueError(f"so_variant must be one of {sorted(_capi.SO_VARIANTS)}")
         # the cross-scale pyramid inside run() (sm_pyramid_config): py_lvl = PY_LEV of main_.cpp:131, applied last
         py_lvl = int(overrides.pop("py_lvl", 1))
+        # the scan-line optimisers' float-minima kernels (sm_create_ex): None is automatic (on where "so" follows GF,
+        # GFNL or BF with inexact sums, as the reference runs them), True / False force it
+        so_float_minima = overrides.pop("so_float_minima", None)
         p = _capi.default_params(max_disp, rows, cols, **overrides)
+        # refine()'s volume-reading stages after "so" read vm[0] as so left it: the context keeps it
+        reads = bool(refine_ext and (dict(refine_ext).get("do_pkr") or dict(refine_ext).get("do_subpixel"))) or \
+            bool(refine_da and dict(refine_da).get("on", True))
+        if p.optimization == _capi.OPTIMIZATIONS["so"] and p.do_refine and reads:
+            p.keep_final_volume = 1
         self.params = p
         self.shape = (rows, cols, p.num_disparities)
-        ctx = C.c_void_p()
-        st = self._lib.sm_create(C.byref(ctx), C.byref(p), device)
+        ctx, st, entry = _capi.create(self._lib, p, device, so_float_minima)
         self._ctx = ctx
-        _capi.check(self._lib, ctx, st, "sm_create")
+        _capi.check(self._lib, ctx, st, entry)
         if tuple(aws) != _capi.AWS_DEFAULTS:
             self.aws_config(*aws)
         if tuple(bf) != _capi.BF_DEFAULTS:
@@ -684,7 +699,8 @@ class StereoBatch:
                           bg_ipl_depth: int = _capi.REFINE_EXT_DEFAULTS[2], do_subpixel: bool = False,
                           se_mode: int = _capi.REFINE_EXT_DEFAULTS[3]):
         """sm_refine_ext_config: refine()'s peak-ratio check, background fill and sub-pixel map (all off by
-        default), from the next run on; needs do_refine = 1."""
+        default), from the next run on; needs do_refine = 1 and, for do_pkr / do_subpixel with optimization "so",
+        keep_final_volume = 1 (the constructor's refine_ext sets it)."""
         st = self._lib.sm_refine_ext_config(self._ctx, int(bool(do_pkr)), float(pkr_ratio), int(disp_pkr),
                                             int(bool(do_bg_ipol)), int(bg_ipl_depth), int(bool(do_subpixel)), int(se_mode))
         _capi.check(self._lib, self._ctx, st, "refine_ext_config")
@@ -693,7 +709,7 @@ class StereoBatch:
                          canny_high: int = _capi.REFINE_DA_DEFAULTS[1], blur_side: int = _capi.REFINE_DA_DEFAULTS[2],
                          blur_centre: int = _capi.REFINE_DA_DEFAULTS[3]):
         """sm_refine_da_config: refine()'s discontinuity adjustment (off by default), from the next run on; needs
-        do_refine = 1 and an optimization other than "so"."""
+        do_refine = 1 and, with optimization "so", keep_final_volume = 1 (the constructor's refine_da sets it)."""
         st = self._lib.sm_refine_da_config(self._ctx, int(bool(on)), int(canny_low), int(canny_high), int(blur_side),
                                            int(blur_centre))
         _capi.check(self._lib, self._ctx, st, "refine_da_config")

@@ -1,8 +1,9 @@
 """ctypes wrapper of the CPU restatement (oracle/sm_oracle.c) — TEST INFRASTRUCTURE ONLY.
 
-PARITY UNPINNED (see sm_oracle.h): the reference cannot be built here and ships no fixtures --
-except NL's median, tree, table and filter, which tests/test_ref_nl.py holds to the reference's own
-NL/ code (oracle/ref_nl.mk, oracle/ref_nl.py).
+PARITY (see sm_oracle.h): the default pipeline -- census codes, arms, censusGrad / Census costs, CBCA, the
+one-level SolveAll sum, SGM, WTA, so -- is held bit for bit to the reference's own functions, built by
+oracle/ref_core.mk (oracle/ref_core.py, tests/test_ref_core.py), and NL's median, tree, table and filter to the
+reference's own NL/ code (oracle/ref_nl.mk, oracle/ref_nl.py, tests/test_ref_nl.py).  The rest is unpinned.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this module.
 """
 from __future__ import annotations
@@ -99,6 +100,11 @@ def load():
         lib.smo_nl_table.argtypes = [C.c_double, P]
         lib.smo_nl_aggregate.argtypes = [C.POINTER(Config), P, P]
         lib.smo_nl_aggregate.restype = C.c_int
+        lib.smo_cbca_view.argtypes = [C.POINTER(Config), P, P, P, C.c_int]
+        lib.smo_solve_all.argtypes = [C.POINTER(Config), P]
+        lib.smo_sgm.argtypes = [C.POINTER(Config), P, P]
+        lib.smo_wta.argtypes = [C.POINTER(Config), P, P]
+        lib.smo_so.argtypes = [C.POINTER(Config), P, P, P]
         _lib = lib
     return _lib
 
@@ -245,6 +251,41 @@ def cost_volume(pair: dict, cfg: Config, view: int = 0) -> np.ndarray:
     out = np.empty((cfg.H, cfg.W, cfg.D), np.float32)
     lib.smo_cost_volume(C.byref(cfg), _p(arr["lbgr"]), _p(arr["rbgr"]), _p(arr["lgray"]), _p(arr["rgray"]), view, _p(out))
     return out
+
+
+def cbca(vm: np.ndarray, arms_l: np.ndarray, arms_r: np.ndarray, cfg: Config, view: int = 0) -> np.ndarray:
+    """smo_cbca_view: cfg.cbca_iters iterations of the intersecting CBCA on one view's volume."""
+    out = np.ascontiguousarray(vm, np.float32).copy()
+    al, ar = np.ascontiguousarray(arms_l, np.uint16), np.ascontiguousarray(arms_r, np.uint16)   # alive over the call
+    load().smo_cbca_view(C.byref(cfg), _p(out), _p(al), _p(ar), view)
+    return out
+
+
+def solve_all(vm: np.ndarray, cfg: Config) -> np.ndarray:
+    out = np.ascontiguousarray(vm, np.float32).copy()
+    load().smo_solve_all(C.byref(cfg), _p(out))
+    return out
+
+
+def sgm(vm: np.ndarray, bgr: np.ndarray, cfg: Config) -> np.ndarray:
+    """smo_sgm: cfg.sgm_paths paths; bgr is the colour image of the volume's own view."""
+    out, img = np.ascontiguousarray(vm, np.float32).copy(), np.ascontiguousarray(bgr, np.uint8)
+    load().smo_sgm(C.byref(cfg), _p(out), _p(img))
+    return out
+
+
+def wta(vm: np.ndarray, cfg: Config) -> np.ndarray:
+    disp, v = np.empty((cfg.H, cfg.W), np.int16), np.ascontiguousarray(vm, np.float32)
+    load().smo_wta(C.byref(cfg), _p(v), _p(disp))
+    return disp
+
+
+def so(vm: np.ndarray, bgr: np.ndarray, cfg: Config):
+    """smo_so: (DP, the accumulated volume)."""
+    out = np.ascontiguousarray(vm, np.float32).copy()
+    disp, img = np.empty((cfg.H, cfg.W), np.int16), np.ascontiguousarray(bgr, np.uint8)
+    load().smo_so(C.byref(cfg), _p(out), _p(disp), _p(img))
+    return disp, out
 
 
 def solve_all_weight(reg_lambda: float = 0.3) -> float:

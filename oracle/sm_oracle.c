@@ -1,10 +1,11 @@
 /*
  * sm_oracle.c — CPU restatement of the reference hot path (TEST INFRASTRUCTURE ONLY).
  *
- * PARITY UNPINNED — see sm_oracle.h.  Only tests/, __graft_entry__.smoke() and bench.py's
+ * PARITY — see sm_oracle.h (the functions of the default pipeline are pinned to the reference's own,
+ * oracle/ref_core.mk).  Only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg may load this library; the product never does.
  *
- * Each function cites the reference lines (relative to /root/reference/) it restates.
+ * Each function cites the reference lines (relative to the reference checkout) it restates.
  * "h" = stereoMatching.h, "cpp" = stereoMatching.cpp, "main" = main_.cpp.
  * Memory-lean but op-order-identical: the h×w×D×5 arm-intersection tensor of
  * genTrueHorVerArms (cpp:2794-2845) is evaluated on the fly (it is a pure min of two

@@ -5,12 +5,15 @@
  * links, loads or calls this code; only tests/, __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg do, and only as the checker / the CPU baseline.
  *
- * PARITY UNPINNED: the reference (xinge456/myStereoMatching, mounted at /root/reference)
- * cannot be built here (needs OpenCV + opencv_contrib/ximgproc + a missing util.h + MSVC-only
- * constructs) and it ships no tests, fixtures or golden vectors.
- * This restatement follows the reference source line by line (citations per function in
- * sm_oracle.c) and is cross-checked against an independent pure-Python restatement
- * (tests/pyref.py) on small inputs; it is not pinned to outputs of the reference binary.
+ * PARITY: the reference (xinge456/myStereoMatching) cannot be built whole (it needs OpenCV +
+ * opencv_contrib/ximgproc + a missing util.h + MSVC-only constructs) and ships no tests,
+ * fixtures or golden vectors.  This restatement follows the reference source line by line
+ * (citations per function in sm_oracle.c).  The default pipeline's functions -- smo_census, smo_arms,
+ * smo_cost_volume (censusGrad, Census), smo_cbca_view, smo_solve_all, smo_sgm, smo_wta, smo_so -- are pinned
+ * bit for bit to the reference's own functions, cut out of a checkout and compiled over a minimal cv::Mat
+ * by oracle/ref_core.mk (tests/test_ref_core.py), and the NL functions to the reference's NL/
+ * code (oracle/ref_nl.mk).  Everything else is cross-checked only against an independent pure-Python
+ * restatement (tests/pyref*.py) on small inputs.
  *
  * Every function is single-threaded, compiled -O2 -ffp-contract=off -fno-fast-math so that
  * each float operation rounds exactly as the reference's scalar C++ does.

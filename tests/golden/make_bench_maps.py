@@ -3,7 +3,7 @@ bench.py workload's batch (rank 0's pairs 0 .. B-1), so that bench.py can compar
 timed loop (the default pipelined two-group schedule) produced, pair by pair, and the GPU tests can
 run whole batches through that schedule against them.
 
-PARITY UNPINNED (see make_golden.py): the maps are the CPU restatement's (oracle/sm_oracle.c).
+The maps are the CPU restatement's (oracle/sm_oracle.c; what pins it: make_golden.py).
 Each record holds the generator arguments, the sha256 of every regenerated input image (checked
 first, so an RNG drift is not mistaken for a kernel bug) and the stacked maps [B, H, W].
 

@@ -1,8 +1,9 @@
 """Generates tests/golden/*.npz from the CPU oracle (oracle/sm_oracle.c).
 
-PARITY UNPINNED: the reference cannot be built or run here and ships no fixtures, so these
-vectors are the oracle's output (itself cross-checked against tests/pyref.py).  They freeze the
-restatement so that any later change to it, or to the GPU path, shows up as a diff.
+The reference cannot be built whole and ships no fixtures, so these vectors are the oracle's output.  The
+oracle's default pipeline is held to the reference's own functions (tests/test_ref_core.py, oracle/ref_core.mk); the
+ADCensus and AD costs of these cases are cross-checked against tests/pyref.py only (parity unpinned).  The vectors
+freeze the restatement so that any later change to it, or to the GPU path, shows up as a diff.
 Run:  python tests/golden/make_golden.py
 """
 import hashlib

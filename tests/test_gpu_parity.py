@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
                 if not os.path.basename(p).startswith(("large_", "bench_maps_",    # those: test_gpu_large_fixtures.py
-                                                       "ref_nl")))                 # that one: test_ref_nl.py
+                                                       "ref_nl", "ref_core")))     # those: test_ref_nl.py, test_ref_core.py
 
 
 def bits(a):

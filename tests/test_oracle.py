@@ -1,7 +1,8 @@
 """The C oracle against the independent numpy restatement (tests/pyref.py) on small inputs.
 
-Both restate the reference (PARITY UNPINNED: no reference binary or fixtures exist); agreement
-of two independent restatements is the pin available here.  Bit-exact comparisons throughout.
+Both restate the reference.  For the default pipeline (census, arms, censusGrad / Census costs, CBCA, SGM, WTA, so)
+the oracle is also held to the reference's own functions (tests/test_ref_core.py, oracle/ref_core.mk); for everything
+else here agreement of two independent restatements is the pin available.  Bit-exact comparisons throughout.
 """
 import numpy as np
 import pytest
